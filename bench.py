@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the render hot path on N MI355X GPUs (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = one frame of the hot path: launch 1 (primary visibility) + launch 2 (path trace) over the
 whole image of the configuration, scene and all per-pixel buffers resident in HBM, results left in
-HBM (the D2H gather of the 12 B/pixel framebuffer is reported separately in `extra`, never in
-`value`).  Default workload = BASELINE.json configs[1]: the 8-sphere Cornell-style scene at
+HBM (with --full the D2H gather of the 12 B/pixel framebuffer is reported separately in `extra`, never
+in `value`).  Default workload = BASELINE.json configs[1]: the 8-sphere Cornell-style scene at
 1920x1080, 4 spp, maxDepth 3, frame 0, ReSTIR reuse off (single frame).
 
 N > 1: the image is cut into 8-row strips dealt round-robin to the ranks (scene replicated, no
@@ -17,7 +17,10 @@ data-path collective; each rank owns its strips of the one frame => total work i
 deterministic).  The K timed steps are enqueued back to back on the rank's HIP stream
 (HRT_FLAG_NO_SYNC) and bracketed by barrier + synchronize; value = rays of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (schema: task contract) with these extra objects:
+A plain run does only what `value` and `ms_per_step` need: set-up, the counting frame, W warm-up and K timed frames, and with
+--dump-outputs DIR the frame the last timed step left on the device (Runner.dump_outputs).
+
+Rank 0 prints ONE JSON line (schema: task contract); --full adds these objects (each takes runs of its own):
   roofline     -- of the path-trace launch (the dominant kernel; for streamed scenes all kernels of the stage).
                   These launches are VALU-bound, not HBM-bound: bound = "valu", achieved = VALU wave-instructions
                   per launch (PMC SQ_INSTS_VALU) / launch time measured live with HIP events on the launch stream,
@@ -68,6 +71,10 @@ PMC_TRANS = ("SQ_INSTS_VALU_TRANS_F32",)
 # sample counts of the PMC child for the 4K configs (their counters are linear in spp: every sample batch does the same work;
 # the roofline scales the counts to the timed frame's spp and says so)
 PMC_CHILD_SPP = {4: 8, 5: 8}
+# --dump-outputs: the per-pixel arrays of the timed frame (name, dtype, components), at most this many bytes in all
+DUMP_ARRAYS = (("color", "int32", 1), ("depth", "float32", 1), ("objectId", "int32", 1), ("radiance", "float32", 3))
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SEED = 0x5EED
 
 
 def algorithmic_bytes(c, n_pixels, launch):
@@ -300,8 +307,9 @@ class Runner:
             dist.all_reduce(b, op=dist.ReduceOp.MAX)
         return a.tolist(), b.tolist()
 
-    def run(self, cfg_id, steps, warmup, spp=0, device_tlas=False, d2h=True):
-        """Counting frame + warm-up + K timed frames of config cfg_id on this rank's strips.  Returns a dict (all ranks)."""
+    def run(self, cfg_id, steps, warmup, spp=0, device_tlas=False, d2h=True, dump_dir=None):
+        """Counting frame + warm-up + K timed frames of config cfg_id on this rank's strips.  Returns a dict (all ranks).
+        dump_dir: write the frame the last timed step left on the device there (dump_outputs)."""
         import numpy as np
         from ilgpu_raytracing_amd import _types as T, engine, scenes
         cfg = scenes.CONFIGS[cfg_id]
@@ -353,6 +361,8 @@ class Runner:
             dt = time.perf_counter() - t0
             ft = r.frame_times(0) + r.frame_times(1)                  # per-frame HIP-event time of both launches (last <= 128 frames)
             frames = max(1, stt.frames)
+            if dump_dir:
+                self.dump_outputs(r, dump_dir)
             path_ms, prim_ms = stt.kernel_ms[1] / frames, stt.kernel_ms[0] / frames
 
             dt_d2h = dt_shared = 0.0
@@ -374,6 +384,41 @@ class Runner:
                     "c1": c1}
         finally:
             r.close()
+
+    def dump_outputs(self, r, out_dir):
+        """The framebuffer the last timed step left on the device -- what hrt_outputs hands a caller: color (0xFFRRGGBB unpacked to
+        R, G, B channels 0..255), depth, objectId, radiance -- as float32 DIR/<name>.npy of shape [H, W(, 3)] (objectId float64
+        where float32 would not hold it exactly).  N > 1: the ranks' strips are all-gathered first and rank 0 writes the whole
+        frame.  Above DUMP_BUDGET_BYTES a fixed, seeded sample of whole rows is written instead, and its row indices as DIR/rows.npy."""
+        import numpy as np
+        from ilgpu_raytracing_amd import tiling
+        torch = self.torch
+        v = r.device_views()
+        h, w = v.height, v.width
+        names = [n for n, _, _ in DUMP_ARRAYS]
+        arrays = [torch.as_tensor(tiling._DeviceArray(getattr(v, n), (h, w * k), dt), device="cuda").clone() for n, dt, k in DUMP_ARRAYS]
+        torch.cuda.synchronize()
+        if self.world > 1:
+            tiling.all_gather_strips(arrays, h, self.world, self.rank)
+        if self.rank != 0:
+            return
+        host = dict(zip(names, (a.cpu().numpy() for a in arrays)))
+        c = host["color"].view(np.uint32)
+        out = {"color": np.stack([(c >> 16) & 255, (c >> 8) & 255, c & 255], axis=-1).astype(np.float32),
+               "depth": host["depth"].astype(np.float32),
+               "objectId": host["objectId"].astype(np.float32),
+               "radiance": host["radiance"].reshape(h, w, 3).astype(np.float32)}
+        if np.abs(host["objectId"]).max(initial=0) >= 1 << 24:                  # not exact in float32
+            out["objectId"] = host["objectId"].astype(np.float64)
+        row_bytes = sum(a[0].nbytes for a in out.values())
+        if row_bytes * h > DUMP_BUDGET_BYTES:
+            n = (DUMP_BUDGET_BYTES - 8 * h - 4096) // row_bytes             # room for rows.npy and the .npy headers
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(h, size=n, replace=False))
+            out = {k: a[rows] for k, a in out.items()}
+            out["rows"] = rows.astype(np.float64)
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in out.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
     def shared_framebuffer_step(self, r, p, cfg, strips, n):
         """End-to-end step with every rank gathering its strips into ONE host framebuffer (the /dev/shm arrays of
@@ -504,6 +549,10 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-strips", default="", help=argparse.SUPPRESS)
     ap.add_argument("--save-pmc", default=None, help="write the measured per-kernel PMC sums to this JSON (profiles/r02_pmc_config<N>.json)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline (PMC passes), "
+                    "cpu_baseline, the D2H-inclusive steps and the extra configs.  --cpu-seconds, --pmc, --extras and --save-pmc act only with --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the frame the last one computed "
+                    "(color, depth, objectId, radiance) as float32 DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.pmc_child:
@@ -526,7 +575,7 @@ def main():
     pmc = None
     pmc_src = {"kind": "none"}
     extra_pmc = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         have_gpu = os.path.exists("/dev/kfd")
         run_ok = args.pmc == "auto" and have_gpu
         pmc_dir = os.path.join(ROOT, "gpurun_out", "bench_pmc_config%d%s" % (args.config, "_tile%d" % world if world > 1 else ""))
@@ -567,10 +616,11 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
 
     R = Runner(args, torch, dist, rank, world, dev_index, rehearsal)
-    main_res = R.run(args.config, args.steps, args.warmup, spp=args.spp, device_tlas=args.device_tlas)
+    main_res = R.run(args.config, args.steps, args.warmup, spp=args.spp, device_tlas=args.device_tlas, d2h=args.full,
+                     dump_dir=args.dump_outputs)
 
     extras = {}
-    if args.extras and args.config == 2 and not args.spp and not args.device_tlas:
+    if args.full and args.extras and args.config == 2 and not args.spp and not args.device_tlas:
         # the other BASELINE configs at their stated size and sample count: fewer steps, same code path
         for name, cid, k, w_ in (("config3", 3, min(args.steps, 20), min(args.warmup, 3)), ("config4_full_spp", 4, min(args.steps, 3), 1),
                                  ("config5_full_spp", 5, min(args.steps, 2), 1)):
@@ -591,33 +641,40 @@ def main():
                        "max_depth": cfg.max_depth, "frame": 0, "restir_reuse": False,
                        "tlas": ("rebuilt on the device (LBVH); picture bit-identical to the uploaded tree's: %s" % main_res["same_picture"]) if args.device_tlas else "as uploaded (reference builder)",
                        "parallelism": "row-strips x%d (8-row strips, round-robin)" % world, "rays_per_step": int(main_res["rays"])},
-            "roofline": roofline_of(main_res, pmc, pmc_src, 1, tile_of=world,
-                                    count_scale=(cfg.spp / float(pmc_src["child_spp"])) if pmc_src.get("child_spp") else 1.0),
             "extra": {"primary_kernel_ms": round(main_res["prim_ms"], 4), "path_trace_kernel_ms": round(main_res["path_ms"], 4),
-                      "frame_event_ms_min": main_res["frame_ms_min"], "frame_event_ms_median": main_res["frame_ms_median"],
-                      "step_ms_with_d2h_gather": round(main_res["d2h_step"] * 1e3, 4),
-                      "mrays_per_s_with_d2h_gather": round(main_res["rays"] / main_res["d2h_step"] / 1e6, 2) if main_res["d2h_step"] > 0 else None,
-                      "step_ms_shared_pinned_framebuffer": round(main_res["shared_step"] * 1e3, 4),
-                      "mrays_per_s_shared_pinned_framebuffer": round(main_res["rays"] / main_res["shared_step"] / 1e6, 2) if main_res["shared_step"] > 0 else None},
+                      "frame_event_ms_min": main_res["frame_ms_min"], "frame_event_ms_median": main_res["frame_ms_median"]},
         }
-        if world == 1 and args.cpu_seconds > 0:
-            out["cpu_baseline"] = cpu_baseline(args.config, cfg, args.cpu_seconds)
-        else:
-            out["cpu_baseline"] = None
-        for name, res in extras.items():
-            if "error" in res:
-                out["extra"][name] = res
-                continue
-            cid = {"config3": 3, "config4_full_spp": 4, "config5_full_spp": 5}[name]
-            cpu = cpu_baseline(cid, res["cfg"], min(6.0, args.cpu_seconds)) if (world == 1 and args.cpu_seconds > 0) else None
-            out["extra"][name] = summary_of(res, world, cpu)
-            if cid in extra_pmc:
-                pm, src = extra_pmc[cid]
-                out["extra"][name]["roofline"] = roofline_of(res, pm, src, 1, count_scale=(res["cfg"].spp / float(src["child_spp"])) if src.get("child_spp") else 1.0)
+        if args.full:
+            add_full_measurements(out, args, world, main_res, pmc, pmc_src, extras, extra_pmc)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def add_full_measurements(out, args, world, main_res, pmc, pmc_src, extras, extra_pmc):
+    """--full: roofline, the D2H-inclusive steps, cpu_baseline and the extra configs, into the result line of rank 0."""
+    cfg = main_res["cfg"]
+    out["roofline"] = roofline_of(main_res, pmc, pmc_src, 1, tile_of=world,
+                                  count_scale=(cfg.spp / float(pmc_src["child_spp"])) if pmc_src.get("child_spp") else 1.0)
+    out["extra"].update({"step_ms_with_d2h_gather": round(main_res["d2h_step"] * 1e3, 4),
+                         "mrays_per_s_with_d2h_gather": round(main_res["rays"] / main_res["d2h_step"] / 1e6, 2) if main_res["d2h_step"] > 0 else None,
+                         "step_ms_shared_pinned_framebuffer": round(main_res["shared_step"] * 1e3, 4),
+                         "mrays_per_s_shared_pinned_framebuffer": round(main_res["rays"] / main_res["shared_step"] / 1e6, 2) if main_res["shared_step"] > 0 else None})
+    if world == 1 and args.cpu_seconds > 0:
+        out["cpu_baseline"] = cpu_baseline(args.config, cfg, args.cpu_seconds)
+    else:
+        out["cpu_baseline"] = None
+    for name, res in extras.items():
+        if "error" in res:
+            out["extra"][name] = res
+            continue
+        cid = {"config3": 3, "config4_full_spp": 4, "config5_full_spp": 5}[name]
+        cpu = cpu_baseline(cid, res["cfg"], min(6.0, args.cpu_seconds)) if (world == 1 and args.cpu_seconds > 0) else None
+        out["extra"][name] = summary_of(res, world, cpu)
+        if cid in extra_pmc:
+            pm, src = extra_pmc[cid]
+            out["extra"][name]["roofline"] = roofline_of(res, pm, src, 1, count_scale=(res["cfg"].spp / float(src["child_spp"])) if src.get("child_spp") else 1.0)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the fields of the task contract plus `roofline` and `cpu_baseline`."""
+"""bench.py prints ONE JSON line with the fields of the task contract; with --full also `roofline` and `cpu_baseline`."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--extras", "0"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--extras", "0", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -42,6 +42,39 @@ def test_bench_json_line():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] == "port" and c["unit"] == "Mrays/s" and c["value"] > 0 and c["cores"] >= 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run times only the headline frame (no roofline, no cpu_baseline, no D2H variants) and --dump-outputs writes the frame
+    of its last timed step: the same arrays whatever --steps is (same arguments, same inputs), float32, within 64 MB."""
+    import numpy as np
+    dumps = []
+    for steps in (4, 1):
+        d = tmp_path / ("steps%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == steps and j["unit"] == "Mrays/s" and j["dtype"] == "f32" and j["higher_is_better"] is True
+        assert j["value"] > 1000 and abs(j["value"] - j["config"]["rays_per_step"] / j["ms_per_step"] / 1e3) / j["value"] < 1e-3
+        assert "roofline" not in j and "cpu_baseline" not in j and "step_ms_with_d2h_gather" not in j["extra"]
+        files = sorted(os.listdir(d))
+        assert files == sorted(["color.npy", "depth.npy", "objectId.npy", "radiance.npy"] + (["rows.npy"] if "rows.npy" in files else []))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        for a in arrs.values():
+            assert a.dtype in (np.float32, np.float64)
+        n_rows = len(arrs["rows"]) if "rows" in arrs else j["config"]["height"]
+        assert arrs["depth"].shape == (n_rows, j["config"]["width"]) and arrs["radiance"].shape == arrs["color"].shape == arrs["depth"].shape + (3,)
+        c = arrs["color"]
+        assert np.all((c >= 0) & (c <= 255) & (c == np.round(c))) and c.max() > 0
+        assert np.all(arrs["objectId"] == np.round(arrs["objectId"]))
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert dumps[0][k].tobytes() == dumps[1][k].tobytes(), k
 
 
 def test_bench_refuses_to_run_without_a_gpu():

@@ -9,7 +9,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
   SECONDS=0
-  timeout -k 10 1100 python bench.py --save-pmc $OUT/pmc_config2.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in ${SECONDS}s"
+  timeout -k 10 1100 python bench.py --full --save-pmc $OUT/pmc_config2.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in ${SECONDS}s"
   python - <<PY
 import json
 j=json.load(open("$OUT/bench.json"))
@@ -34,7 +34,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = profiles ]; then
   done
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = rehearsal ]; then
-  HRT_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 3 > $OUT/bench_rehearsal2.json 2> $OUT/bench_rehearsal2.err; echo "rehearsal rc=$?"
+  HRT_BENCH_REHEARSAL=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 3 --full > $OUT/bench_rehearsal2.json 2> $OUT/bench_rehearsal2.err; echo "rehearsal rc=$?"
   python - <<PY
 import json
 try:
