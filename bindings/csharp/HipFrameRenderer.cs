@@ -40,6 +40,19 @@ namespace ILGPU_Raytracing.Engine
             return _display;
         }
 
+        /// <summary>Picking: the closest hit under pixel (x, y) of a width x height frame (row 0 = bottom row) seen through `cam`, the
+        /// camera the frame was rendered with.  The ray is the primary-visibility launch's pixel-centre ray (RTRay.cs:120-126,
+        /// Ray.GenerateRay RTUtils.cs:13-17), so the hit is what the G-buffer holds at that pixel.</summary>
+        public HrtRayHit Pick(in Camera cam, int width, int height, int x, int y)
+        {
+            float u = (x + 0.5f) / Math.Max(1, width), v = (y + 0.5f) / Math.Max(1, height);
+            Ray r = Ray.GenerateRay(cam, u, v);
+            var ray = new HrtRay { origin = r.origin, dir = r.dir, tMax = 1e30f };
+            HrtRayHit hit;
+            HipRaytrace.Check(_ctx, HipRaytrace.hrt_trace_rays(_ctx, HipRaytrace.HRT_QUERY_CLOSEST, &ray, 1, &hit, -1, null));
+            return hit;
+        }
+
         /// <summary>Framebuffer.EnsureLength / RTTaa.Ensure side effect the host may want explicitly (camera cut).</summary>
         public void ResetHistory() => HipRaytrace.Check(_ctx, HipRaytrace.hrt_reset_history(_ctx));
 

@@ -77,6 +77,22 @@ namespace ILGPU_Raytracing.Engine
         public int blas_action; public float blas_growth;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtRay                         // hrt_ray (32 bytes): Ray (RTUtils.cs:6-10) without invDir, plus ShadowOcclusion's tMaxWorld
+    {
+        public Float3 origin; public float tMax;   // tMax: occlusion queries only
+        public Float3 dir; public float pad;       // dir as given, not normalised
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtRayHit                      // hrt_ray_hit (48 bytes): TraceClosest's out parameters (SceneDeviceViews.cs:30-86) + what was hit
+    {
+        public float t; public Float3 normal;      // miss: t = 1e30, normal = 0
+        public Float3 albedo; public float ior;    // miss: albedo = 1, ior = 1
+        public int objId, shade;                   // bestObjId / bestShade (miss: -1 / 0)
+        public int instance, prim;                 // instance record; sphere or triangle index (miss: -1 / -1)
+    }
+
     internal static unsafe class HipRaytrace
     {
         const string Lib = "hip_raytrace";        // libhip_raytrace.so
@@ -104,6 +120,10 @@ namespace ILGPU_Raytracing.Engine
         [DllImport(Lib)] public static extern int hrt_frame_times(IntPtr ctx, int dev, int launch, float* ms, int cap, int* n);
         [DllImport(Lib)] public static extern int hrt_set_workspace_limit(IntPtr ctx, long maxResidentPaths);
         [DllImport(Lib)] public static extern int hrt_device_count();
+        // SceneDeviceViews.TraceClosest / ShadowOcclusion over caller rays: query 0 = closest (results: HrtRayHit[n]), 1 = occluded
+        // (results: int[n] of 0/1).  dev < 0: host arrays, split over every device slot; dev >= 0: device pointers of that slot.  Blocking.
+        public const int HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1;
+        [DllImport(Lib)] public static extern int hrt_trace_rays(IntPtr ctx, int query, HrtRay* rays, long n, void* results, int dev, float* deviceMs);
 
         // native asset loader (optional: a C# host may keep MeshLoaderOBJ)
         [DllImport(Lib)] public static extern IntPtr hrth_scene_new();

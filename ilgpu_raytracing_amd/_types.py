@@ -165,6 +165,21 @@ class PresentParams(C.Structure):
 PRESENT_RESAMPLE, PRESENT_TAAU = 0, 1
 
 
+class Ray(C.Structure):               # hrt_ray: a ray of hrt_trace_rays
+    _fields_ = [("origin", Float3), ("tMax", C.c_float), ("dir", Float3), ("pad", C.c_float)]
+
+
+class RayHit(C.Structure):            # hrt_ray_hit: TraceClosest's outputs + the instance record and primitive hit
+    _fields_ = [("t", C.c_float), ("normal", Float3), ("albedo", Float3), ("ior", C.c_float),
+                ("objId", C.c_int32), ("shade", C.c_int32), ("instance", C.c_int32), ("prim", C.c_int32)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 48
+
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1      # hrt_ray_query
+QUERY_CHUNK = 1 << 21                     # HRT_QUERY_CHUNK: rays per walk of one device slot
+
+
 FLAG_COUNTERS = 1
 FLAG_SKIP_PRIMARY = 2
 FLAG_REFERENCE_LAYOUT = 4

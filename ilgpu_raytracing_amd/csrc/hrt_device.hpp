@@ -382,8 +382,9 @@ struct TracerRef {
     DScene S;
 
 // TraceClosest + TraverseBLAS_* (SceneDeviceViews.cs:30-86,124-237)
+// win (may be NULL, ray queries): receives what the winner is, {instance record, sphere or triangle index}; untouched on a miss
 template <bool COUNT>
-HRT_D bool closest(const Ray& wray, Hit& best, Cnt<COUNT>& C) const
+HRT_D bool closest(const Ray& wray, Hit& best, Cnt<COUNT>& C, int* win = nullptr) const
 {
     C.inc(C_RAYS_CLOSEST);
     best.t = 1e30f; best.n = mk3(0.f, 0.f, 0.f); best.albedo = mk3(1.f, 1.f, 1.f); best.objId = -1; best.shade = 0; best.ior = 1.f;
@@ -521,6 +522,7 @@ HRT_D bool closest(const Ray& wray, Hit& best, Cnt<COUNT>& C) const
                             best.t = tWorld;
                             best.n = normalize(xform_vector(inst->objectToWorld, nObj));
                             best.albedo = alb; best.objId = objId; best.shade = shade; best.ior = ior;
+                            if (win) { win[0] = S.tlasInst[i]; win[1] = prim; }
                         }
                     }
                 }

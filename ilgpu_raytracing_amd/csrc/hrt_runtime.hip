@@ -25,6 +25,7 @@
 #include "hrt_walker_tl.hpp"
 #include "hrt_bvh.hpp"
 #include "hrt_post.hpp"
+#include "hrt_query.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
 #include "../../include/hrt_test_hooks.h"
@@ -487,6 +488,11 @@ struct DeviceState {
     int row_begin = 0, row_end = 0;            // rows [row_begin,row_end) ...
     int strip_n = 1, strip_i = 0;              // ... of which this device owns 8-row strips s with s % strip_n == strip_i
     int n_strips = 0;
+    // ray queries (hrt_trace_rays): one chunk of rays in flight, allocated on the first query and grown on demand; separate from the
+    // frame's buffers, so hrt_device_views pointers never move because of a query
+    void* q_mem = nullptr; int64_t q_cap = 0;             // rays (32 B) + raw winners (16 B) + hits (48 B) per ray, then 8 hand-out counters
+    void* q_host = nullptr; int64_t q_host_cap = 0;       // pinned staging of the host path: rays + hits per ray
+    hipEvent_t q_ev[2] = {};
 };
 
 } // namespace
@@ -1498,6 +1504,162 @@ constexpr int64_t kAnyTreeMinInstances = 256;       // scenes of fewer instances
 constexpr int64_t kHostSahMaxInstances = (int64_t)1 << HRT_SAH_MAX_LOG2;
 int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, int64_t nSlots, bool instOnce, const SahTopology* pre = nullptr, const hrt_instance* hostInst = nullptr);       // defined with the scene-update code below
 
+// ---------------------------------------------------------------------------------------
+// Ray queries (hrt_trace_rays, kernels in hrt_query.hpp).  Rays are walked in chunks of at most kQueryChunk, so the memory a query
+// holds is bounded for any n; a 1920x1080 set of rays is one chunk.
+// ---------------------------------------------------------------------------------------
+constexpr int64_t kQueryChunk = HRT_QUERY_CHUNK;
+constexpr size_t kQueryDevBytes = 32 + 16 + 48, kQueryHostBytes = 32 + 48;
+
+void free_query(DeviceState& d)
+{
+    if (d.q_mem) (void)hipFree(d.q_mem);
+    if (d.q_host) (void)hipHostFree(d.q_host);
+    for (hipEvent_t& e : d.q_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    d.q_mem = nullptr; d.q_host = nullptr; d.q_cap = d.q_host_cap = 0;
+}
+
+// device staging for m rays (and the pinned host staging too when `host`); the caller has made d's device current
+int ensure_query(hrt_ctx* c, DeviceState& d, int64_t m, bool host)
+{
+    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
+    if (d.q_cap < m)
+    {
+        if (d.q_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.q_mem); d.q_mem = nullptr; d.q_cap = 0; }
+        HIPCHK(c, hipMalloc(&d.q_mem, (size_t)m * kQueryDevBytes + 8 * kQueryGrabStride * sizeof(int)));
+        d.q_cap = m;
+    }
+    if (host && d.q_host_cap < m)
+    {
+        if (d.q_host) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipHostFree(d.q_host); d.q_host = nullptr; d.q_host_cap = 0; }
+        HIPCHK(c, hipHostMalloc(&d.q_host, (size_t)m * kQueryHostBytes, hipHostMallocPortable));
+        d.q_host_cap = m;
+    }
+    return HRT_OK;
+}
+
+template <int F>
+void launch_query_packed(const DeviceState& d, int query, const QueryK& q, hipStream_t st)
+{
+    TracerPackedT<F> tr; tr.P = d.dpacked; tr.S = d.dscene;
+    const dim3 block(256), gridR((unsigned)((q.n + 255) / 256));
+    const dim3 gridW((unsigned)std::min<long long>((q.nSegs + 3) / 4, (long long)d.n_cu * kWalkBlocksPerCU));     // persistent waves, as a chained walk
+    const bool lt3 = F != 0 && d.dpacked.leafTris == 3;           // triangle records per leaf step, chosen at upload (DPacked::leafTris)
+    if (query == HRT_QUERY_OCCLUDED)
+    {
+        if (lt3) hipLaunchKernelGGL((hrt_query_occluded_kernel<F, (F != 0 ? 3 : 2)>), gridW, block, 0, st, tr, q);
+        else     hipLaunchKernelGGL((hrt_query_occluded_kernel<F, 2>), gridW, block, 0, st, tr, q);
+        return;
+    }
+    if (lt3) hipLaunchKernelGGL((hrt_query_closest_kernel<F, (F != 0 ? 3 : 2)>), gridW, block, 0, st, tr, q);
+    else     hipLaunchKernelGGL((hrt_query_closest_kernel<F, 2>), gridW, block, 0, st, tr, q);
+    hipLaunchKernelGGL((hrt_query_finish_kernel<F>), gridR, block, 0, st, tr, q);
+}
+
+// rays with a non-finite origin or direction, which the packed walks leave out (hrt_query.hpp), on the reference's arrays
+void launch_query_fixup(const DeviceState& d, int query, const QueryK& q, hipStream_t st)
+{
+    TracerRef t; t.S = d.dscene;
+    const dim3 block(256), gridR((unsigned)((q.n + 255) / 256));
+    if (query == HRT_QUERY_OCCLUDED) hipLaunchKernelGGL((hrt_query_ref_kernel<true, true>), gridR, block, 0, st, t, q);
+    else                             hipLaunchKernelGGL((hrt_query_ref_kernel<false, true>), gridR, block, 0, st, t, q);
+}
+
+// the walk (+ finish) of q.n <= kQueryChunk rays already on the device; q.raw / q.grab point into d's staging
+int launch_query(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const QueryK& q, hipStream_t st)
+{
+    if (cc.packed_ok)
+    {
+        HIPCHK(c, hipMemsetAsync(q.grab, 0, 8 * kQueryGrabStride * sizeof(int), st));
+        if (cc.packed_feat == 0)      launch_query_packed<0>(d, query, q, st);
+        else if (cc.packed_feat == 1) launch_query_packed<1>(d, query, q, st);
+        else                          launch_query_packed<3>(d, query, q, st);
+        launch_query_fixup(d, query, q, st);
+    }
+    else
+    {
+        TracerRef t; t.S = d.dscene;
+        const dim3 block(256), gridR((unsigned)((q.n + 255) / 256));
+        if (query == HRT_QUERY_OCCLUDED) hipLaunchKernelGGL((hrt_query_ref_kernel<true, false>), gridR, block, 0, st, t, q);
+        else                             hipLaunchKernelGGL((hrt_query_ref_kernel<false, false>), gridR, block, 0, st, t, q);
+    }
+    HIPCHK(c, hipGetLastError());
+    return HRT_OK;
+}
+
+// rays [begin, end) of one device slot, chunk by chunk: H2D, walk, finish, D2H on the slot's main stream (after any frame in flight).
+// dev_ptrs: rays / results are device memory of this slot.  *ms += the HIP-event time of the kernels.
+int query_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const hrt_ray* rays, void* results, int64_t begin, int64_t end,
+               bool dev_ptrs, float* ms)
+{
+    HIPCHK(c, hipSetDevice(d.device_id));
+    const size_t resBytes = query == HRT_QUERY_CLOSEST ? sizeof(hrt_ray_hit) : sizeof(int32_t);
+    auto registered = [&](const void* p, size_t bytes) {
+        for (const auto& r : cc.pinned) if ((const char*)p >= r.first && (const char*)p + bytes <= r.first + r.second) return true;
+        return false;
+    };
+    const hipStream_t st = d.stream;
+    for (int64_t off = begin; off < end; off += kQueryChunk)
+    {
+        const int64_t m = std::min<int64_t>(kQueryChunk, end - off);
+        int rc = ensure_query(c, d, m, !dev_ptrs);
+        if (rc != HRT_OK) return rc;
+        char* base = (char*)d.q_mem;
+        QueryK q;
+        q.raw = (float4*)(base + (size_t)d.q_cap * 32);
+        q.grab = (int*)(base + (size_t)d.q_cap * kQueryDevBytes);
+        q.n = (int)m; q.nSegs = (int)((m + kQuerySeg - 1) / kQuerySeg);
+        const hrt_ray* src = rays + off;
+        char* dst = (char*)results + (size_t)off * resBytes;
+        const bool rayReg = !dev_ptrs && registered(src, (size_t)m * sizeof(hrt_ray));
+        const bool resReg = !dev_ptrs && registered(dst, (size_t)m * resBytes);
+        char* hostRays = (char*)d.q_host;
+        char* hostRes = (char*)d.q_host + (size_t)d.q_host_cap * 32;
+        if (dev_ptrs)
+        {
+            q.rays = (const float4*)src;
+            q.hits = (float4*)dst; q.occ = (int32_t*)dst;
+        }
+        else
+        {
+            q.rays = (const float4*)base;
+            q.hits = (float4*)(base + (size_t)d.q_cap * 48); q.occ = (int32_t*)q.hits;
+            if (!rayReg) std::memcpy(hostRays, src, (size_t)m * sizeof(hrt_ray));
+            HIPCHK(c, hipMemcpyAsync(base, rayReg ? (const void*)src : (const void*)hostRays, (size_t)m * sizeof(hrt_ray), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
+        rc = launch_query(c, cc, d, query, q, st);
+        if (rc != HRT_OK) return rc;
+        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
+        if (!dev_ptrs) HIPCHK(c, hipMemcpyAsync(resReg ? (void*)dst : (void*)hostRes, q.hits, (size_t)m * resBytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        float t = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
+        *ms += t;
+        if (!dev_ptrs && !resReg) std::memcpy(dst, hostRes, (size_t)m * resBytes);
+    }
+    return HRT_OK;
+}
+
+// dev < 0 reads and writes through the host: device memory there would be dereferenced by the CPU
+bool in_device_memory(const void* p)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }       // unknown to HIP: pageable host memory
+    return a.type == hipMemoryTypeDevice;
+}
+
+// dev >= 0 takes device memory of that slot only: a host pointer, another device's memory or a range that runs past its allocation is refused
+bool on_device(const DeviceState& d, const void* p, size_t bytes)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (a.type != hipMemoryTypeDevice || a.device != d.device_id) return false;
+    hipDeviceptr_t lo = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&lo, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (const char*)p >= (const char*)lo && (const char*)p + bytes <= (const char*)lo + size;
+}
+
 } // namespace
 
 extern "C" {
@@ -1591,6 +1753,7 @@ void hrt_destroy(hrt_ctx* c)
         free_scene(d);
         free_workspace(d);
         free_present(d);
+        free_query(d);
         if (d.counters) (void)hipFree(d.counters);
         for (int f = 0; f < DeviceState::kRing; f++)
             for (int k = 0; k < 4; k++) if (d.ev[f][k]) (void)hipEventDestroy(d.ev[f][k]);
@@ -2864,6 +3027,63 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_device_buffers"); }
+
+int hrt_trace_rays(hrt_ctx* c, int32_t query, const hrt_ray* rays, int64_t n, void* results, int32_t dev, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (query != HRT_QUERY_CLOSEST && query != HRT_QUERY_OCCLUDED) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: unknown query");
+    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: n must be >= 0");
+    if (n > 0 && (!rays || !results)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: rays and results are needed when n > 0");
+    const int nd = (int)c->dev.size();
+    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: device slot out of range");
+    if (n == 0) return HRT_OK;
+    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_rays: no scene uploaded (call hrt_scene_upload first)");
+    const size_t resBytes = query == HRT_QUERY_CLOSEST ? sizeof(hrt_ray_hit) : sizeof(int32_t);
+    if (dev >= 0)
+    {
+        DeviceState& d = c->dev[(size_t)dev];
+        HIPCHK(c, hipSetDevice(d.device_id));
+        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, results, (size_t)n * resBytes))
+            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: with dev >= 0, rays and results must be device memory of that slot's device, large enough for n");
+        if (((uintptr_t)rays | (uintptr_t)results) & 15) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: device rays and results must be 16-byte aligned");
+        float ms = 0.f;
+        int rc = query_slot(c, *c, d, query, rays, results, 0, n, true, &ms);
+        if (rc != HRT_OK) return rc;
+        if (device_ms) *device_ms = ms;
+        return HRT_OK;
+    }
+    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as the frame's gather)
+    if (in_device_memory(rays) || in_device_memory(results))
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: with dev < 0, rays and results must be host memory (pass the slot of device pointers as dev)");
+    std::vector<float> ms((size_t)nd, 0.f);
+    auto part = [&](int i) { return n * i / nd; };
+    if (nd > 1)
+    {
+        std::vector<int> rcs((size_t)nd, HRT_OK);
+        std::vector<std::string> errs((size_t)nd);
+        std::vector<std::thread> workers;
+        for (int i = 0; i < nd; i++)
+            workers.emplace_back([&, i]() {
+                try
+                {
+                    rcs[(size_t)i] = query_slot(nullptr, *c, c->dev[(size_t)i], query, rays, results, part(i), part(i + 1), false, &ms[(size_t)i]);
+                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
+                }
+                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
+            });
+        for (std::thread& t : workers) t.join();
+        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_rays: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
+    }
+    else
+    {
+        int rc = query_slot(c, *c, c->dev[0], query, rays, results, 0, n, false, &ms[0]);
+        if (rc != HRT_OK) return rc;
+    }
+    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_trace_rays"); }
 
 #ifdef HRT_TEST_HOOKS
 // test hook: evaluate hrt_math.h function `fn` on device 0 of ctx (see hrt_math_probe_kernel)

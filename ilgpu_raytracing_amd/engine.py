@@ -63,6 +63,7 @@ def _load(path, hooks=False):
     L.hrt_host_register.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.hrt_host_unregister.argtypes = [C.c_void_p, C.c_void_p]
     L.hrt_set_workspace_limit.argtypes = [C.c_void_p, C.c_int64]
+    L.hrt_trace_rays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
     L.hrt_device_count.restype = C.c_int
     L.hrt_version.restype = C.c_char_p
     L.hrth_scene_new.restype = C.c_void_p
@@ -359,6 +360,9 @@ class RTRenderer:
         self.prev_camera = copy_camera(self.camera)
         self.scene = None
         self.last_params = None
+        self.device_ids = ids
+        self.last_made_params = None          # FrameParams of the last make_params (RTRenderer.pick casts its camera's rays)
+        self.last_query_ms = 0.0              # device time of the last trace_rays (HIP events, max over device slots)
         if build_default_scene:
             s = Scene()
             s.build_default_scene()
@@ -473,6 +477,7 @@ class RTRenderer:
         p.rngLockNoise = temporal_seed
         p.spp = self.spp
         p.maxDepth = self.max_depth
+        self.last_made_params = p
         return p
 
     def render_params(self, params, outputs=None, flags=0, rows=None, strips=None):
@@ -546,6 +551,95 @@ class RTRenderer:
         self._check(self._L.hrt_device_buffers(self._ctx, slot, C.byref(v)))
         return v
 
+    def trace_rays(self, origins, dirs, tmax=None, query="closest", slot=None):
+        """SceneDeviceViews.TraceClosest / ShadowOcclusion (SceneDeviceViews.cs:30-121) on the scene now on the device, one result per ray
+        (hrt_trace_rays).  origins, dirs: (n, 3) float32; dirs are used as given (t is in units of |dir|).  tmax: ShadowOcclusion's
+        tMaxWorld, a float or (n,) float32 (default +inf); closest-hit queries have none (TraceClosest starts at 1e30).
+        numpy inputs: host path over every device slot; returns a structured array of T.RayHit ("closest") or int32 0/1 ("occluded").
+        torch tensors on a GPU: device path on the slot of their device (`slot` picks one of several); returns torch tensors, no host copy:
+        "closest" -> dict t, normal, albedo, ior (float32), objId, shade, instance, prim (int32); "occluded" -> int32 (n,).
+        A process that hands torch tensors over imports torch before this library is loaded: torch's HIP runtime is then the process's."""
+        q = _QUERIES.get(query)
+        if q is None:
+            raise ValueError("query must be one of %s, not %r" % (sorted(_QUERIES), query))
+        if type(origins).__module__.split(".")[0] == "torch" or type(dirs).__module__.split(".")[0] == "torch":
+            return self._trace_rays_torch(q, origins, dirs, tmax, slot)
+        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
+        if slot is not None:
+            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        n = o.shape[0]
+        rays = np.zeros((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        rays[:, 3] = _tmax_arg(tmax, n)
+        out = np.zeros(n, T.np_dtype(T.RayHit)) if q == T.QUERY_CLOSEST else np.zeros(n, np.int32)
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_rays(self._ctx, q, rays.ctypes.data if n else None, n, out.ctypes.data if n else None, -1, C.byref(ms)))
+        self.last_query_ms = ms.value
+        return out
+
+    def _trace_rays_torch(self, q, origins, dirs, tmax, slot):
+        import torch                                       # lazy: the host path needs no torch
+        if not (isinstance(origins, torch.Tensor) and isinstance(dirs, torch.Tensor)):
+            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
+        for name, a in (("origins", origins), ("dirs", dirs)):
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
+            if a.device.type != "cuda":
+                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
+        if origins.shape != dirs.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
+        if origins.device != dirs.device:
+            raise ValueError("origins and dirs live on different devices")
+        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+        slots = [i for i, d in enumerate(self.device_ids) if d == dev]
+        if slot is None:
+            if not slots:
+                raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
+            slot = slots[0]
+        elif slot not in slots:
+            raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
+        n = origins.shape[0]
+        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
+        rays[:, 0:3], rays[:, 4:7] = origins, dirs
+        if tmax is None or isinstance(tmax, (int, float, np.floating)):
+            rays[:, 3] = float("inf") if tmax is None else float(np.float32(tmax))
+        else:
+            tm = torch.as_tensor(tmax, device=origins.device)
+            if tm.dtype != torch.float32 or tuple(tm.shape) != (n,):
+                raise ValueError("tmax must be a float or an (n,) float32 array")
+            rays[:, 3] = tm
+        out = torch.zeros((n, 12) if q == T.QUERY_CLOSEST else (n,), dtype=torch.float32 if q == T.QUERY_CLOSEST else torch.int32,
+                          device=origins.device)
+        torch.cuda.synchronize(origins.device)               # the library works on its own streams
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_rays(self._ctx, q, rays.data_ptr() if n else None, n, out.data_ptr() if n else None, slot, C.byref(ms)))
+        self.last_query_ms = ms.value
+        if q != T.QUERY_CLOSEST:
+            return out
+        ints = out[:, 8:12].view(torch.int32)
+        return dict(t=out[:, 0], normal=out[:, 1:4], albedo=out[:, 4:7], ior=out[:, 7],
+                    objId=ints[:, 0], shade=ints[:, 1], instance=ints[:, 2], prim=ints[:, 3])
+
+    def pick(self, width, height, x, y):
+        """The closest hit under pixel (x, y) of a width x height image (row 0 = bottom row): the pixel-centre primary ray of the
+        primary-visibility launch (RTRay.cs:120-126, Ray.GenerateRay RTUtils.cs:13-17) from the camera of the last make_params,
+        traced with trace_rays.  Returns one T.RayHit record (numpy)."""
+        if self.last_made_params is None:
+            raise RuntimeError("pick needs the camera of a frame: call make_params / render_frame first")
+        cam = self.last_made_params.cam
+        f = np.float32
+        v3 = lambda a: (f(a.X), f(a.Y), f(a.Z))
+        u = (f(x) + f(0.5)) / f(max(1, width))
+        v = (f(y) + f(0.5)) / f(max(1, height))
+        ll, hz, vt, org = v3(cam.lowerLeft), v3(cam.horizontal), v3(cam.vertical), v3(cam.origin)
+        d = [((ll[k] + hz[k] * u) + vt[k] * v) - org[k] for k in range(3)]
+        inv = f(1.0) / np.sqrt(max(f(1e-20), (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))        # Normalize, Float3.cs:91-95
+        o = np.array([org], np.float32)
+        dd = np.array([[d[0] * inv, d[1] * inv, d[2] * inv]], np.float32)
+        return self.trace_rays(o, dd)[0]
+
     def math_exhaustive(self, which):
         """(mismatches, bits of the first one) of a trimmed device function against its IEEE definition over its whole domain."""
         n, first = C.c_uint64(0), C.c_uint32(0)
@@ -561,6 +655,30 @@ class RTRenderer:
 
 
 # ------------------------------------------------------------------ SceneManager / BvhManager (Engine/SceneManager.cs, BvhManager.cs)
+_QUERIES = {"closest": T.QUERY_CLOSEST, "occluded": T.QUERY_OCCLUDED}
+
+
+def _rays_arg(a, name):
+    if not isinstance(a, np.ndarray):
+        raise TypeError("%s must be a numpy array or a torch tensor, got %s" % (name, type(a).__name__))
+    if a.dtype != np.float32:
+        raise ValueError("%s must be float32, got %s" % (name, a.dtype))
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s must have shape (n, 3), got %s" % (name, a.shape))
+    return a
+
+
+def _tmax_arg(tmax, n):
+    if tmax is None:
+        return np.float32(np.inf)
+    if np.isscalar(tmax):
+        return np.float32(tmax)
+    t = np.asarray(tmax)
+    if t.dtype != np.float32 or t.shape != (n,):
+        raise ValueError("tmax must be a float or an (n,) float32 array, got %s %s" % (t.dtype, t.shape))
+    return t
+
+
 class SceneManager:
     """SceneManager (SceneManager.cs:12-38) over one RTRenderer: Scene, BuildDefaultScene, LoadObjInstance, Commit(policy),
     ReplaceScene.  Commit is BvhManager.BuildOrRefit (BvhManager.cs:27) with the RebuildPolicy honoured: the first commit, and

@@ -30,6 +30,8 @@
  *                          (TAAU, blit) without leaving the device  RTRenderer.cs:155-161,208-231
  *   hrt_reset_history      Framebuffer.EnsureLength re-allocation on resize (fresh
  *                          reservoirs)                           Framebuffer.cs:60-97
+ *   hrt_trace_rays         SceneDeviceViews.TraceClosest / ShadowOcclusion over caller rays
+ *                                                                SceneDeviceViews.cs:30-121
  *   hrt_destroy            RTRenderer.Dispose                    RTRenderer.cs:347-363
  *   hrt_last_error         the exception message of CudaException / Argument*Exception
  *
@@ -285,6 +287,24 @@ int  hrt_host_unregister(hrt_ctx* ctx, void* ptr);
 int  hrt_set_workspace_limit(hrt_ctx* ctx, int64_t max_resident_paths);
 
 int  hrt_device_buffers(hrt_ctx* ctx, int dev, hrt_device_views* out);
+
+/* ---- ray queries on the scene now on the device (hrt_ray / hrt_ray_hit in hrt_types.h).
+ * HRT_QUERY_CLOSEST: SceneDeviceViews.TraceClosest(ray, out ...) (SceneDeviceViews.cs:30-86): closestT starts at 1e30 with the
+ *   fixed 0.001 epsilon (no tMax); result i = hrt_ray_hit of ray i, plus the instance record and primitive that won.
+ * HRT_QUERY_OCCLUDED: ShadowOcclusion(ray, ray.tMax) (SceneDeviceViews.cs:89-121) with the any-hit alpha cut-outs (:270-327);
+ *   result i = 1 if ray i is occluded, else 0.  Any float tMax is legal (0, negative, NaN, +-inf: what the slab and t tests make of it).
+ * results: hrt_ray_hit[n] (CLOSEST) or int32_t[n] (OCCLUDED).
+ * dev < 0: rays / results are host memory; the rays are split into contiguous chunks over every device slot, each slot works in
+ *   fixed-size chunks through its own pinned staging (or straight from / to a range registered with hrt_host_register).
+ * dev >= 0: rays / results are device memory of device slot `dev` (checked; host memory -> HRT_ERR_INVALID_ARG), 16-byte aligned.
+ * Blocking.  device_ms (may be NULL): HIP-event time of the device work (max over slots), copies excluded.
+ * Queries leave frame state alone (G-buffer, reservoirs, present history, hrt_frame_times, hrt_device_views pointers); they run on
+ * the device streams after any frames enqueued with HRT_FLAG_NO_SYNC, whose accounting stays with hrt_synchronize.
+ * n == 0 launches nothing. */
+enum hrt_ray_query { HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1 };
+#define HRT_QUERY_CHUNK (1 << 21)      /* rays per walk: a device slot works through its rays in chunks of at most this many */
+int  hrt_trace_rays(hrt_ctx* ctx, int32_t query, const hrt_ray* rays, int64_t n, void* results,
+                    int32_t dev, float* device_ms);
 int  hrt_reset_history(hrt_ctx* ctx);           /* zero both reservoir sets */
 
 /* Test hooks (math probes, host-side builders of derived trees) are declared in hrt_test_hooks.h and exist only in

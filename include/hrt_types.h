@@ -200,4 +200,25 @@ typedef struct hrt_stats {
     int32_t reserved;
 } hrt_stats;
 
+/*
+ * Ray queries on the uploaded scene (hrt_trace_rays): the two device methods every frame is built from,
+ * SceneDeviceViews.TraceClosest(Ray, out ...) and ShadowOcclusion(Ray, tMaxWorld) (SceneDeviceViews.cs:30-121),
+ * for rays the host supplies.  The ray is Ray (RTUtils.cs:6-10) without invDir, which is derived as the kernels
+ * derive it (InvDir, RTRay.cs:548-549).
+ */
+typedef struct hrt_ray {            /* 32 bytes: two 16-byte loads                                            */
+    hrt_float3 origin; float tMax;  /* tMax: occlusion queries only (ShadowOcclusion's tMaxWorld)             */
+    hrt_float3 dir;    float pad;   /* dir is used as given, not normalised (t is in units of |dir|)          */
+} hrt_ray;
+
+typedef struct hrt_ray_hit {        /* 48 bytes: TraceClosest's out parameters plus what it hit               */
+    float t; hrt_float3 normal;     /* miss: t = 1e30, normal = (0,0,0)                                       */
+    hrt_float3 albedo; float ior;   /* miss: albedo = (1,1,1), ior = 1                                        */
+    int32_t objId, shade;           /* TraceClosest's bestObjId / bestShade (miss: -1 / 0)                    */
+    int32_t instance, prim;         /* instance record index; sphere index or triangle index (miss: -1 / -1)  */
+} hrt_ray_hit;
+
+HRT_STATIC_ASSERT(sizeof(hrt_ray) == 32, "hrt_ray is 32 bytes");
+HRT_STATIC_ASSERT(sizeof(hrt_ray_hit) == 48, "hrt_ray_hit is 48 bytes");
+
 #endif /* HRT_TYPES_H */
