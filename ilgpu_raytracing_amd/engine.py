@@ -6,7 +6,7 @@ C# host's role from Python with the same class / method names and argument meani
 
     Scene.AddSphere / BuildSphereInstance / LoadObjInstance* / RebuildTLAS / BuildDefaultScene
     SceneManager.Commit  ->  RTRenderer.commit(scene)      (Scene.UploadAll, Scene.cs:258-279)
-    RTRenderer.RenderDirectToPbo(pbo, w, h, frame, dt) -> RTRenderer.render_frame(w, h, frame, dt, outputs)
+    RTRenderer.RenderDirectToPbo(pbo, w, h, frame, dt) -> RTRenderer.render_direct(w, h, frame, dt); its host half is FrameHost
     RTRenderer.SetSunParams, Camera.CreateCamera / look-at ctor / Translate
 
 (* the array-append half; the OBJ file parser is out of scope.)
@@ -328,9 +328,114 @@ class Scene:
 
 
 # ------------------------------------------------------------------ RTRenderer (Engine/RTRenderer.cs)
-class RTRenderer:
-    """Frame orchestration of RTRenderer.RenderDirectToPbo up to the end-of-frame Synchronize
-    (RTRenderer.cs:105-205,233).  Presentation (PBO map, TAAU/blit) is out of scope."""
+def _host_fmin(a, b):
+    """.NET Math.Min on floats (XMath.Min on the host, include/hrt_math.h hrt_host_fmin): a NaN operand is returned, -0 < +0."""
+    if a != a: return a
+    if b != b: return b
+    if a == b: return a if np.signbit(a) else b
+    return a if a < b else b
+
+
+def _host_fmax(a, b):
+    """.NET Math.Max on floats (hrt_host_fmax)."""
+    if a != a: return a
+    if b != b: return b
+    if a == b: return b if np.signbit(a) else a
+    return a if a > b else b
+
+
+TWO_PI_F = np.float32(6.28318530717958647692)                 # RTRenderer.cs:171, a float constant
+
+
+class FrameHost:
+    """The host half of RTRenderer.RenderDirectToPbo (RTRenderer.cs:43-61, 104-236) without a device: the private fields with their
+    defaults, the internal size, the camera bake, the float32 sun animation and the FrameParams assembly.  Needs the library's host
+    functions (camera, sun direction) but no GPU; RTRenderer inherits it."""
+
+    def __init__(self, width=1280, height=720):
+        # private fields of the reference's RTRenderer (RTRenderer.cs:43-61), same defaults; `float` fields are numpy float32
+        self.render_scale = np.float32(0.67)
+        self.enable_taau = True
+        self.enable_temporal_reuse = 1
+        self.enable_spatial_reuse = 1
+        self.rng_lock_noise = 1
+        self.spp = 2
+        self.max_depth = 3                                        # RTRenderer.cs:204, a local constant there
+        self.sun_azimuth = np.float32(0.0)
+        self.sun_elevation = np.float32(0.9)
+        self.sun_speed = np.float32(0.0)
+        self.dir_light_radiance = (10.0, 10.0, 10.0)
+        self.sky_tint_top = (0.5, 0.7, 1.0)
+        self.sky_tint_bottom = (1.0, 1.0, 1.0)
+        self.camera = create_camera(max(1, width), max(1, height), 60.0)
+        camera_translate(self.camera, (1.0, 0.0, -4.0))           # RTRenderer.cs:78-79
+        self.prev_camera = copy_camera(self.camera)
+        self.last_made_params = None          # FrameParams of the last make_params (RTRenderer.pick casts its camera's rays)
+
+    def set_sun_params(self, speed_rad_per_sec, elevation_rad):
+        """RTRenderer.SetSunParams (RTRenderer.cs:99-103): both are float fields."""
+        self.sun_speed = np.float32(speed_rad_per_sec)
+        self.sun_elevation = np.float32(elevation_rad)
+
+    def internal_size(self, out_width, out_height, render_scale=None):
+        """inW, inH of RenderDirectToPbo (RTRenderer.cs:109-116): max(1, (int)XMath.Round(out * scale)) in float, ties to even."""
+        s = np.float32(self.render_scale if render_scale is None else render_scale)
+        out_w, out_h = max(1, out_width), max(1, out_height)
+        return (max(1, int(np.rint(np.float32(out_w) * s))), max(1, int(np.rint(np.float32(out_h) * s))))
+
+    def advance_sun(self, dt):
+        """The sun animation of RenderDirectToPbo (RTRenderer.cs:169-172), all in float: dt clamped by XMath.Clamp = Max(Min(dt, 0.1f), 0f)
+        with the host's Min / Max (a NaN dt stays NaN), one wrap by the float 2*pi."""
+        with np.errstate(all="ignore"):
+            dtc = _host_fmax(_host_fmin(np.float32(dt), np.float32(0.1)), np.float32(0.0))
+            az = np.float32(self.sun_azimuth) + np.float32(self.sun_speed) * dtc
+            if az >= TWO_PI_F:
+                az = az - TWO_PI_F
+            elif az < np.float32(0.0):
+                az = az + TWO_PI_F
+        self.sun_azimuth = np.float32(az)
+        return self.sun_azimuth
+
+    def make_params(self, width, height, frame, dt=0.0):
+        """Parameter assembly of RenderDirectToPbo (RTRenderer.cs:119-202) at an internal size of width x height."""
+        w, h = max(1, width), max(1, height)
+        bake_camera_derived(self.camera, w, h)
+        bake_camera_derived(self.prev_camera, w, h)
+        temporal_seed = 0 if self.rng_lock_noise == 0 else random.randint(-2 ** 31, 2 ** 31 - 2)    # Random.Shared.Next(int.MinValue, int.MaxValue)
+        self.advance_sun(dt)
+        p = T.FrameParams()
+        p.width, p.height, p.frame = w, h, frame
+        p.cam = copy_camera(self.camera)
+        p.prevCam = copy_camera(self.prev_camera)
+        p.dirLightDir = T.f3(*sun_direction(self.sun_azimuth, self.sun_elevation))
+        p.dirLightRadiance = T.f3(*self.dir_light_radiance)
+        p.skyTintTop = T.f3(*self.sky_tint_top)
+        p.skyTintBottom = T.f3(*self.sky_tint_bottom)
+        p.debugCamSeq = 0
+        p.enableTemporalReuse = self.enable_temporal_reuse
+        p.enableSpatialReuse = self.enable_spatial_reuse
+        p.rngLockNoise = temporal_seed
+        p.spp = self.spp
+        p.maxDepth = self.max_depth
+        self.last_made_params = p
+        return p
+
+    def end_frame(self):
+        """_prevCamera = _camera (RTRenderer.cs:236)."""
+        self.prev_camera = copy_camera(self.camera)
+
+    def host_frame(self, out_width, out_height, frame, dt=0.0, render_scale=None):
+        """Everything RenderDirectToPbo does on the host for one frame, in its order: (FrameParams, inW, inH); the camera hand-off
+        of the frame's end included.  RTRenderer.render_direct runs the device work between make_params and end_frame."""
+        in_w, in_h = self.internal_size(out_width, out_height, render_scale)
+        p = self.make_params(in_w, in_h, frame, dt)
+        self.end_frame()
+        return p, in_w, in_h
+
+
+class RTRenderer(FrameHost):
+    """Frame orchestration of RTRenderer.RenderDirectToPbo (RTRenderer.cs:105-236) over one hrt_ctx; the host half is FrameHost.
+    The PBO map of the presentation step is out of scope (present() returns the display image)."""
 
     def __init__(self, device_ids=None, width=1280, height=720, build_default_scene=False, library=None):
         L = self._L = library or lib()
@@ -342,26 +447,10 @@ class RTRenderer:
             raise HrtError(rc, (L.hrt_last_error(None) or b"").decode())
         self._ctx = h
         self.n_devices = len(ids)
-        # private fields of the reference's RTRenderer (RTRenderer.cs:43-61), same defaults except
-        # render scale (benchmarks render at 1.0) -- callers set what they need
-        self.enable_temporal_reuse = 1
-        self.enable_spatial_reuse = 1
-        self.rng_lock_noise = 1
-        self.spp = 2
-        self.max_depth = 3
-        self.sun_azimuth = 0.0
-        self.sun_elevation = 0.9
-        self.sun_speed = 0.0
-        self.dir_light_radiance = (10.0, 10.0, 10.0)
-        self.sky_tint_top = (0.5, 0.7, 1.0)
-        self.sky_tint_bottom = (1.0, 1.0, 1.0)
-        self.camera = create_camera(max(1, width), max(1, height), 60.0)
-        camera_translate(self.camera, (1.0, 0.0, -4.0))           # RTRenderer.cs:78-79
-        self.prev_camera = copy_camera(self.camera)
+        FrameHost.__init__(self, width, height)
         self.scene = None
         self.last_params = None
         self.device_ids = ids
-        self.last_made_params = None          # FrameParams of the last make_params (RTRenderer.pick casts its camera's rays)
         self.last_query_ms = 0.0              # device time of the last trace_rays (HIP events, max over device slots)
         if build_default_scene:
             s = Scene()
@@ -445,41 +534,6 @@ class RTRenderer:
         self._check(self._L.hrt_scene_download_tlas(self._ctx, slot, nodes, cnt[0], idx, cnt[1], inst, cnt[2], cnt))
         return nodes, idx, inst, tuple(cnt)
 
-    def set_sun_params(self, speed_rad_per_sec, elevation_rad):
-        """RTRenderer.SetSunParams (RTRenderer.cs:99-103)."""
-        self.sun_speed = speed_rad_per_sec
-        self.sun_elevation = elevation_rad
-
-    def make_params(self, width, height, frame, dt=0.0):
-        """Parameter assembly of RenderDirectToPbo (RTRenderer.cs:109-202) at render scale 1."""
-        w, h = max(1, width), max(1, height)
-        bake_camera_derived(self.camera, w, h)
-        bake_camera_derived(self.prev_camera, w, h)
-        temporal_seed = 0 if self.rng_lock_noise == 0 else random.randint(-2 ** 31, 2 ** 31 - 2)
-        dtc = min(max(dt, 0.0), 0.1)
-        self.sun_azimuth += self.sun_speed * dtc
-        two_pi = 6.28318530717958647692
-        if self.sun_azimuth >= two_pi:
-            self.sun_azimuth -= two_pi
-        elif self.sun_azimuth < 0.0:
-            self.sun_azimuth += two_pi
-        p = T.FrameParams()
-        p.width, p.height, p.frame = w, h, frame
-        p.cam = copy_camera(self.camera)
-        p.prevCam = copy_camera(self.prev_camera)
-        p.dirLightDir = T.f3(*sun_direction(self.sun_azimuth, self.sun_elevation))
-        p.dirLightRadiance = T.f3(*self.dir_light_radiance)
-        p.skyTintTop = T.f3(*self.sky_tint_top)
-        p.skyTintBottom = T.f3(*self.sky_tint_bottom)
-        p.debugCamSeq = 0
-        p.enableTemporalReuse = self.enable_temporal_reuse
-        p.enableSpatialReuse = self.enable_spatial_reuse
-        p.rngLockNoise = temporal_seed
-        p.spp = self.spp
-        p.maxDepth = self.max_depth
-        self.last_made_params = p
-        return p
-
     def render_params(self, params, outputs=None, flags=0, rows=None, strips=None):
         """The two launches + sync for an explicit FrameParams.  Returns Stats.
         rows=(y0,y1) restricts the frame to a row range, strips=(n,i) to every n-th 8-row strip of it;
@@ -493,10 +547,11 @@ class RTRenderer:
         return st
 
     def render_frame(self, width, height, frame, dt=0.0, outputs=None, flags=0, rows=None):
-        """RenderDirectToPbo(pbo, width, height, frame, dt) without the presentation step."""
+        """RenderDirectToPbo(pbo, width, height, frame, dt) without the presentation step, with width x height as the internal size
+        (a render scale of 1); render_direct applies the render scale."""
         p = self.make_params(width, height, frame, dt)
         st = self.render_params(p, outputs, flags, rows)
-        self.prev_camera = copy_camera(self.camera)             # RTRenderer.cs:236
+        self.end_frame()
         return st
 
     def synchronize(self):
@@ -535,13 +590,17 @@ class RTRenderer:
         self._check(self._L.hrt_present(self._ctx, C.byref(pp), out.ctypes.data))
         return out
 
-    def render_direct(self, out_width, out_height, frame, dt=0.0, render_scale=0.67, taau=True, flags=0):
-        """RenderDirectToPbo(pbo, width, height, frame, dt) end to end: internal size = round(out * renderScale)
-        (RTRenderer.cs:113-116), the two launches, then the presentation step.  Returns (display colour, Stats)."""
-        in_w = max(1, int(np.rint(np.float32(out_width) * np.float32(render_scale))))
-        in_h = max(1, int(np.rint(np.float32(out_height) * np.float32(render_scale))))
-        st = self.render_frame(in_w, in_h, frame, dt, None, flags)
-        return self.present(out_width, out_height, taau), st
+    def render_direct(self, out_width, out_height, frame, dt=0.0, render_scale=None, taau=None, flags=0, outputs=None):
+        """RenderDirectToPbo(pbo, width, height, frame, dt) end to end: internal size = round(out * renderScale) (RTRenderer.cs:109-116;
+        render_scale / taau default to the fields render_scale = 0.67f / enable_taau), the two launches, then the presentation step.
+        outputs (optional, internal size) also receives the internal arrays.  Returns (display colour, Stats)."""
+        out_w, out_h = max(1, out_width), max(1, out_height)
+        in_w, in_h = self.internal_size(out_w, out_h, render_scale)
+        p = self.make_params(in_w, in_h, frame, dt)
+        st = self.render_params(p, outputs, flags)
+        out = self.present(out_w, out_h, self.enable_taau if taau is None else taau)
+        self.end_frame()
+        return out, st
 
     def reset_history(self):
         self._check(self._L.hrt_reset_history(self._ctx))

@@ -191,12 +191,22 @@ class OrcScene:
         return T.arrays_from_scene_desc(self.desc())
 
 
+def default_threads():
+    """CPUs this process may run on (its affinity mask, not the machine's count), capped by OMP_NUM_THREADS when that is set."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        cap = int(os.environ.get("OMP_NUM_THREADS", "0").split(",")[0])
+    except ValueError:
+        cap = 0
+    return max(1, min(n, cap) if cap > 0 else n)
+
+
 def render_frame(scene_desc, params, out_struct, prev_struct=None, row_begin=0, row_end=0, run_primary=True, nthreads=None):
     """Runs PrimaryVisibilityKernel + PathTraceKernel of the oracle.  Returns Stats.
     run_primary: True both launches, False launch 2 only (G-buffer as given), 2 launch 1 only."""
     st = T.Stats()
     if nthreads is None:
-        nthreads = min(os.cpu_count() or 1, 64)
+        nthreads = default_threads()
     rc = lib().orc_render_frame(C.byref(scene_desc), C.byref(params), row_begin, row_end, 2 if run_primary == 2 else (1 if run_primary else 0), nthreads,
                                 C.byref(out_struct), C.byref(prev_struct) if prev_struct is not None else None, C.byref(st))
     if rc != 0:

@@ -440,3 +440,111 @@ def sun_dir(math, azimuth, elevation):                                          
     with np.errstate(all="ignore"):
         az, el = f32(azimuth), f32(elevation)
         return normalize((math("cos", az) * math("cos", el), math("sin", el), math("sin", az) * math("cos", el)))
+
+
+def camera_create(math, width, height, fov_degrees):                                     # Camera.cs:19-47 CreateCamera
+    with np.errstate(all="ignore"):
+        aspect = f32(width) / f32(max(1, height))
+        theta = f32(fov_degrees) * (PI / f32(180))
+        half_h = math("tan", f32(0.5) * theta)
+        half_w = aspect * half_h
+        origin, look_at, up_hint = v3(0, 1, 3), v3(0, 0.5, 0), v3(0, 1, 0)
+        w = normalize(_sub(origin, look_at))
+        u = normalize(_cross(up_hint, w))
+        v = _cross(w, u)
+        cam = {"origin": origin, "lowerLeft": _sub(_sub(_sub(origin, _mul(u, half_w)), _mul(v, half_h)), w),
+               "horizontal": _mul(u, f32(2) * half_w), "vertical": _mul(v, f32(2) * half_h)}
+        return _update_derived(cam, aspect, theta)
+
+
+def _update_derived(cam, aspect, fov_y):                                                 # Camera.cs UpdateDerived
+    with np.errstate(all="ignore"):
+        c = dict(cam)
+        c["forward"] = normalize(_sub(_add(_add(c["lowerLeft"], _mul(c["horizontal"], f32(0.5))), _mul(c["vertical"], f32(0.5))), c["origin"]))
+        c["up"] = normalize(c["vertical"])
+        c["right"] = normalize(_cross(c["forward"], c["up"]))
+        c["aspect"], c["fovYRadians"] = f32(aspect), f32(fov_y)
+        return c
+
+
+def camera_translate(cam, delta):                                                        # Camera.cs:121-126 Translate
+    with np.errstate(all="ignore"):
+        d = v3(*delta)
+        c = dict(cam)
+        c["origin"], c["lowerLeft"] = _add(c["origin"], d), _add(c["lowerLeft"], d)
+        return _update_derived(c, c["aspect"], c["fovYRadians"])
+
+
+def round_half_even(x):                                                                  # XMath.Round on a float: MathF.Round, ties to even
+    r = math.floor(float(x))
+    d = float(x) - r
+    if d > 0.5 or (d == 0.5 and r % 2 != 0):
+        r += 1
+    return int(r)
+
+
+class HostFrames:
+    """RTRenderer.RenderDirectToPbo's host code (RTRenderer.cs:43-61, 75-79, 99-236) for one window: the private float fields, the
+    internal size, the two camera bakes, the dt-driven sun, the IntegratorParams and the camera hand-off, as float32 Python.
+    frame() returns what the integrator launch receives, as a FrameParams, plus (inW, inH)."""
+
+    TWO_PI = f32(6.28318530717958647692)
+
+    def __init__(self, math, window_w, window_h):
+        self.math = math
+        self.render_scale = f32(0.67)
+        self.enable_temporal_reuse, self.enable_spatial_reuse, self.rng_lock_noise, self.spp = 1, 1, 1, 2
+        self.sun_azimuth, self.sun_elevation, self.sun_speed = f32(0), f32(0.9), f32(0)
+        cam = camera_create(math, max(1, window_w), max(1, window_h), 60)
+        self.camera = camera_translate(cam, (1, 0, -4))
+        self.prev_camera = self.camera
+
+    def set_sun_params(self, speed, elevation):
+        self.sun_speed, self.sun_elevation = f32(speed), f32(elevation)
+
+    def translate(self, delta):
+        self.camera = camera_translate(self.camera, delta)
+
+    def frame(self, width, height, frame, dt, seed=None):
+        """seed: the temporal seed when noise is animated (Random.Shared.Next(int.MinValue, int.MaxValue)); None draws one."""
+        with np.errstate(all="ignore"):
+            out_w, out_h = max(1, width), max(1, height)
+            in_w = max(1, round_half_even(f32(out_w) * self.render_scale))
+            in_h = max(1, round_half_even(f32(out_h) * self.render_scale))
+            self.camera = camera_bake(self.math, self.camera, in_w, in_h)
+            self.prev_camera = camera_bake(self.math, self.prev_camera, in_w, in_h)
+            cam = self.camera
+            if self.rng_lock_noise == 0:
+                temporal_seed = 0
+            else:
+                temporal_seed = int(np.random.randint(-2 ** 31, 2 ** 31 - 1)) if seed is None else seed
+            dt = f32(dt)
+            dt_clamped = nmax(nmin(dt, f32(0.1)), f32(0))                                # XMath.Clamp = Max(Min(v, hi), lo), host Min / Max
+            self.sun_azimuth = self.sun_azimuth + self.sun_speed * dt_clamped
+            if self.sun_azimuth >= self.TWO_PI:
+                self.sun_azimuth = self.sun_azimuth - self.TWO_PI
+            elif self.sun_azimuth < f32(0):
+                self.sun_azimuth = self.sun_azimuth + self.TWO_PI
+            sun = sun_dir(self.math, self.sun_azimuth, self.sun_elevation)
+            p = T.FrameParams()
+            p.width, p.height, p.frame = in_w, in_h, frame
+            p.cam, p.prevCam = _camera_struct(cam), _camera_struct(self.prev_camera)
+            p.dirLightDir = T.Float3(*[float(x) for x in sun])
+            p.dirLightRadiance = T.Float3(10, 10, 10)
+            p.skyTintTop = T.Float3(0.5, 0.7, 1.0)
+            p.skyTintBottom = T.Float3(1.0, 1.0, 1.0)
+            p.debugCamSeq = 0
+            p.enableSpatialReuse, p.enableTemporalReuse = self.enable_spatial_reuse, self.enable_temporal_reuse
+            p.rngLockNoise = temporal_seed
+            p.spp = self.spp
+            p.maxDepth = 3
+            self.prev_camera = self.camera
+            return p, in_w, in_h
+
+
+def _camera_struct(c):
+    out = T.Camera()
+    for k in ("origin", "lowerLeft", "horizontal", "vertical", "forward", "right", "up"):
+        setattr(out, k, T.Float3(*[float(x) for x in c[k]]))
+    out.aspect, out.fovYRadians = float(c["aspect"]), float(c["fovYRadians"])
+    return out
