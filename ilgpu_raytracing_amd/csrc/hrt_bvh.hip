@@ -133,11 +133,9 @@ __global__ void __launch_bounds__(kBlock) k_leaf_slots(TlasDevice T)
 // One thread per node.  In walk-order numbering the subtree of node i is the index range [i, skip(i)), so a node whose
 // subtree has at most T.directMax nodes takes its box straight from the instances of the leaves in that range
 // (BuildTLASNodeRecursive's own loop over its items, Scene.cs:472-480) -- no ordering between threads at all for the
-// bottom five levels, which hold 31 of every 32 nodes; k_refit_level finishes the rest.  Only a tree that is not numbered
-// in walk order (HRT_BUILDER_ORDER) climbs: leaves report to their parent through one arrival counter, the last child to
-// arrive unites the children (the chain left, left.skip, ... up to the parent's own skip link) and climbs on; release /
-// acquire at agent scope costs an L2 write-back per step on a multi-XCD part (300 us for a 131 k-node tree when every
-// node climbed).  min / max are exact: no order can change a bit.
+// bottom five levels, which hold 31 of every 32 nodes; k_refit_level finishes the rest.  Every tree the device refits is
+// numbered in walk order (the upload renumbers the host's tree; the LBVH and the host SAH builder emit that order), so no
+// thread waits for another.  min / max are exact: no order can change a bit.
 HRT_D int subtree_size(const TlasDevice& T, int i)
 {
     const int sk = node_skip(T.tlas, i);
@@ -150,8 +148,8 @@ __global__ void __launch_bounds__(kBlock) k_refit(TlasDevice T)
     if (i >= T.nT) return;
     NodeQ* nodes = T.tlas;
     const int cnt = node_cnt(nodes, i);
-    const int size = cnt > 0 ? 1 : (T.directMax > 1 ? subtree_size(T, i) : T.nT + 1);
-    if (size > T.directMax || size < 1) return;              // waits for its children (size < 1: not a walk-order subtree)
+    const int size = cnt > 0 ? 1 : subtree_size(T, i);
+    if (size > T.directMax || size < 1) return;              // left to k_refit_level (size < 1: a skip link that points back)
     F3 mn = mk3(FLT_MAX, FLT_MAX, FLT_MAX), mx = mk3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
     for (int j = i; j < i + size; j++)
     {
@@ -165,30 +163,9 @@ __global__ void __launch_bounds__(kBlock) k_refit(TlasDevice T)
     }
     nodes[i].lo.x = mn.x; nodes[i].lo.y = mn.y; nodes[i].lo.z = mn.z;
     nodes[i].hi.x = mx.x; nodes[i].hi.y = mx.y; nodes[i].hi.z = mx.z;
-    int cur = i;
-    for (;;)
-    {
-        const int p = T.parent[cur];
-        if (p < 0) break;
-        if (T.directMax > 1) break;                            // walk-order tree: k_refit_level takes over above the direct subtrees
-        const int old = __hip_atomic_fetch_add(T.arrive + p, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old + 1 < T.nchild[p]) break;
-        const int pskip = node_skip(nodes, p);
-        mn = mk3(FLT_MAX, FLT_MAX, FLT_MAX); mx = mk3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
-        int c = node_link(nodes, p) & kEnd;
-        for (int guard = 0; c != kEnd && c != pskip && guard < 64; guard++)
-        {
-            const float4 lo = nodes[c].lo, hi = nodes[c].hi;
-            mn = min3(mn, mk3(lo.x, lo.y, lo.z)); mx = max3(mx, mk3(hi.x, hi.y, hi.z));
-            c = f2i(hi.w) & kEnd;
-        }
-        nodes[p].lo.x = mn.x; nodes[p].lo.y = mn.y; nodes[p].lo.z = mn.z;
-        nodes[p].hi.x = mx.x; nodes[p].hi.y = mx.y; nodes[p].hi.z = mx.z;
-        cur = p;
-    }
 }
 
-// Walk-order trees need no arrival counters at all: a node whose subtree has more than `lo` and at most `hi` nodes unites the
+// Above the direct subtrees: a node whose subtree has more than `lo` and at most `hi` nodes unites the
 // boxes of the maximal subtrees of at most `lo` nodes inside its index range (finished by the previous launch), hopping over
 // each of them with its skip link.  With lo = 63, 63 * 64, ... three or four launches reach the root of any tree, every
 // thread reads at most a few hundred boxes, and a kernel boundary is the only synchronisation.
@@ -454,7 +431,7 @@ __global__ void __launch_bounds__(kBlock) k_tri_records(BlasDevice B)
 }
 
 // Same scheme as k_refit: subtrees of up to directMax nodes straight from their triangles (BoundsOfTriangle over the
-// node's items, Scene.cs:423-429,597-605), arrival counters above.
+// node's items, Scene.cs:423-429,597-605), k_blas_refit_level above.
 __global__ void __launch_bounds__(kBlock) k_blas_refit(BlasDevice B, int kind)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -486,27 +463,6 @@ __global__ void __launch_bounds__(kBlock) k_blas_refit(BlasDevice B, int kind)
     }
     nodes[i].lo.x = mn.x; nodes[i].lo.y = mn.y; nodes[i].lo.z = mn.z;
     nodes[i].hi.x = mx.x; nodes[i].hi.y = mx.y; nodes[i].hi.z = mx.z;
-    int cur = i;
-    for (;;)
-    {
-        const int p = B.parent[cur];
-        if (p < 0) break;
-        if (B.directMax > 1) break;                            // k_blas_refit_level takes over above the direct subtrees
-        const int old = __hip_atomic_fetch_add(B.arrive + p, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old + 1 < B.nchild[p]) break;
-        const int pskip = node_skip(nodes, p);
-        mn = mk3(FLT_MAX, FLT_MAX, FLT_MAX); mx = mk3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
-        int c = node_link(nodes, p) & kEnd;
-        for (int guard = 0; c != kEnd && c != pskip && guard < 64; guard++)
-        {
-            const float4 lo = nodes[c].lo, hi = nodes[c].hi;
-            mn = min3(mn, mk3(lo.x, lo.y, lo.z)); mx = max3(mx, mk3(hi.x, hi.y, hi.z));
-            c = f2i(hi.w) & kEnd;
-        }
-        nodes[p].lo.x = mn.x; nodes[p].lo.y = mn.y; nodes[p].lo.z = mn.z;
-        nodes[p].hi.x = mx.x; nodes[p].hi.y = mx.y; nodes[p].hi.z = mx.z;
-        cur = p;
-    }
 }
 
 __global__ void __launch_bounds__(kBlock) k_blas_refit_level(BlasDevice B, int kind, int lo, int hi)
@@ -789,8 +745,7 @@ hipError_t blas_rebuild_mesh(const TlasDevice& T, const BlasDevice& B, const Mes
     k_leaf_counts<<<blocks_for(2 * n - 1), kBlock, 0, s>>>(T, n);
     if ((e = hipMemcpyAsync(counts, T.leafCounts, sizeof(counts), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    int limit = 4;                                   // the reference's BLAS leaf size; HRT_BLAS_LEAF_LIMIT = 4..14 for experiments
-    if (const char* e2 = HRT_ENV("HRT_BLAS_LEAF_LIMIT")) { const int v = atoi(e2); if (v >= 4 && v <= 14) limit = v; }
+    int limit = 4;                                   // the reference's BLAS leaf size
     while (limit < 14 && 2 * counts[limit] - 1 > J.nodeCap) limit++;
     if (2 * counts[limit] - 1 > J.nodeCap) return hipErrorInvalidValue;
     if (leafLimitOut) *leafLimitOut = limit;
@@ -806,13 +761,10 @@ hipError_t blas_rebuild_mesh(const TlasDevice& T, const BlasDevice& B, const Mes
 
 hipError_t blas_refit(const BlasDevice& B, int kind, hipStream_t s)
 {
-    hipError_t e;
-    if (B.directMax <= 1 && (e = hipMemsetAsync(B.arrive, 0, (size_t)B.nB * sizeof(int), s)) != hipSuccess) return e;   // only the climb counts arrivals
     if (kind == 1 && B.nSlots > 0) k_tri_records<<<blocks_for(B.nSlots), kBlock, 0, s>>>(B);
     k_blas_refit<<<blocks_for(B.nB), kBlock, 0, s>>>(B, kind);
-    if (B.directMax > 1)
-        for (long long lo = B.directMax; lo < B.maxRange[kind]; lo *= 64)
-            k_blas_refit_level<<<blocks_for(B.nB), kBlock, 0, s>>>(B, kind, (int)lo, (int)std::min<long long>(lo * 64, 0x7FFFFFFF));
+    for (long long lo = B.directMax; lo < B.maxRange[kind]; lo *= 64)
+        k_blas_refit_level<<<blocks_for(B.nB), kBlock, 0, s>>>(B, kind, (int)lo, (int)std::min<long long>(lo * 64, 0x7FFFFFFF));
     k_blas_derive<<<blocks_for(B.nB), kBlock, 0, s>>>(B, kind);
     return hipGetLastError();
 }
@@ -878,8 +830,7 @@ hipError_t tlas_rebuild_topology(TlasDevice& T, hipStream_t s, int* leavesOut)
     // Karras over the single instances; subtrees of <= 2 instances become the leaves (see the BLAS rebuild)
     k_lbvh_inner<<<blocks_for(n - 1), kBlock, 0, s>>>(T, n, 1);
     if ((e = hipMemsetAsync(T.lstart, 0, (size_t)(n + 1) * sizeof(int), s)) != hipSuccess) return e;
-    int limit = 2;                                   // the reference's TLAS leaf size; HRT_TLAS_LEAF_LIMIT = 1..14 for experiments
-    if (const char* e2 = HRT_ENV("HRT_TLAS_LEAF_LIMIT")) { const int v = atoi(e2); if (v >= 1 && v <= 14) limit = v; }
+    const int limit = 2;                             // the reference's TLAS leaf size
     k_mark_leaves<<<blocks_for(2 * n - 1), kBlock, 0, s>>>(T, n, limit);
     bytes = T.iscanTmpBytes;
     if ((e = hipcub::DeviceScan::ExclusiveSum(T.iscanTmp, bytes, (const int*)T.lstart, T.lsum, n + 1, s)) != hipSuccess) return e;
@@ -960,12 +911,10 @@ hipError_t tlas_finish(const TlasDevice& T, hipStream_t s)
 {
     hipError_t e;
     if ((e = hipMemsetAsync(T.flags, 0, 4 * sizeof(int), s)) != hipSuccess) return e;
-    if (T.directMax <= 1 && (e = hipMemsetAsync(T.arrive, 0, (size_t)T.nT * sizeof(int), s)) != hipSuccess) return e;   // only the climb counts arrivals
     if (T.nTI > 0) k_leaf_slots<<<blocks_for(T.nTI), kBlock, 0, s>>>(T);
     k_refit<<<blocks_for(T.nT), kBlock, 0, s>>>(T);
-    if (T.directMax > 1)
-        for (long long lo = T.directMax; lo < T.nT; lo *= 64)
-            k_refit_level<<<blocks_for(T.nT), kBlock, 0, s>>>(T, (int)lo, (int)std::min<long long>(lo * 64, 0x7FFFFFFF));
+    for (long long lo = T.directMax; lo < T.nT; lo *= 64)
+        k_refit_level<<<blocks_for(T.nT), kBlock, 0, s>>>(T, (int)lo, (int)std::min<long long>(lo * 64, 0x7FFFFFFF));
     k_scan_input<<<blocks_for(T.nT), kBlock, 0, s>>>(T);
     size_t bytes = T.scanTmpBytes;
     if ((e = hipcub::DeviceScan::ExclusiveSum(T.scanTmp, bytes, (const unsigned long long*)T.scanIn, T.scanOut, T.nT, s)) != hipSuccess) return e;

@@ -158,9 +158,6 @@ constexpr int kWalkBlocksPerCU2 = HRT_WALK_BLOCKS_PER_CU_2LANES;
 // left (chained, RangeGrab).  Measured, path stage of configs 3 / 4 / 5: static 33.5 / 56.4 / 32.8 ms, chained
 // 36.2 / 37.2 / 21.7 ms: the triangle scenes gain 1.5x from full lanes, the sphere-instance scene is bound by L1
 // accesses (more live lanes do not help it) and loses the L1 sharing of four neighbouring ranges per workgroup.
-#ifndef HRT_CHAIN_FEAT0
-#define HRT_CHAIN_FEAT0 0
-#endif
 #ifndef HRT_WF_TRACE_WAVES
 #define HRT_WF_TRACE_WAVES 4
 #endif
@@ -775,7 +772,6 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
     // walk visits the same nodes in the same order.  perm[old - lo] = new - lo.
     auto walk_order = [&](const hrt_bvh_node* src, int64_t lo, int64_t hi, int64_t root, std::vector<int32_t>& perm) -> int32_t {   // returns the number of reachable nodes
         const size_t n = (size_t)(hi - lo);
-        if (HRT_ENV("HRT_BUILDER_ORDER")) { perm.resize(n); for (size_t i = 0; i < n; i++) perm[i] = (int32_t)i; return -1; }   // A/B knob
         perm.assign(n, -1);
         int32_t next = 0;
         std::vector<int64_t> st;
@@ -825,7 +821,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
         auto skipq = [&](size_t i) { return __builtin_bit_cast(int, out.tlas[i].hi.w) & kEnd; };
         for (size_t i = 0; i < (size_t)nT; i++)
         {
-            if (cntq(i) > 0) { if (reachableT < 0 || (int32_t)i < reachableT) out.reach_leaves++; continue; }
+            if (cntq(i) > 0) { if ((int32_t)i < reachableT) out.reach_leaves++; continue; }
             int c = __builtin_bit_cast(int, out.tlas[i].lo.w) & kEnd;
             const int end = skipq(i);
             int steps = 0;
@@ -842,7 +838,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
         bool once = nT > 0 && out.refit_ok;
         for (size_t i = 0; once && i < (size_t)nT; i++)
         {
-            if (cntq(i) == 0 || !(reachableT < 0 || (int32_t)i < reachableT)) continue;
+            if (cntq(i) == 0 || (int32_t)i >= reachableT) continue;
             const int first = __builtin_bit_cast(int, out.tlas[i].lo.w);
             for (int j = 0; j < cntq(i); j++)
             {
@@ -861,7 +857,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
                    c.lo.x >= p.lo.x && c.lo.y >= p.lo.y && c.lo.z >= p.lo.z && c.hi.x <= p.hi.x && c.hi.y <= p.hi.y && c.hi.z <= p.hi.z;
         };
         for (size_t i = 1; i < (size_t)nT; i++)
-            if ((reachableT < 0 || (int32_t)i < reachableT) && out.parent[i] >= 0 && !inside(out.tlas[i], out.tlas[(size_t)out.parent[i]])) out.nested = false;
+            if ((int32_t)i < reachableT && out.parent[i] >= 0 && !inside(out.tlas[i], out.tlas[(size_t)out.parent[i]])) out.nested = false;
     }
     alloc_nodes(nB, out.blas);
     {
@@ -906,7 +902,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
                 // maintenance arrays for the BLAS of a triangle mesh (device refit after a vertex update, hrt_bvh.hpp)
                 const uint8_t kind = rangeKind[(size_t)(&r - ranges.data())];
                 if (kind != 1 && kind != 2) { if (kind != 0) out.blas_refit_ok = false; continue; }               // shared between a mesh and a sphere set, or of an unknown type
-                if (reach != (int32_t)(r.second - r.first)) { out.blas_refit_ok = false; continue; }              // unreachable nodes or builder numbering
+                if (reach != (int32_t)(r.second - r.first)) { out.blas_refit_ok = false; continue; }              // unreachable nodes
                 for (int64_t k = r.first; k < r.second; k++) out.bkind[(size_t)k] = kind;
                 if (kind == 1) out.meshRanges.push_back(r);
                 out.max_range[kind] = std::max(out.max_range[kind], (int)(r.second - r.first));
@@ -1030,7 +1026,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
     out.tlasX.assign(1, NodeQ{});
     bool leavesFit = true;                   // count code 15 marks an instance record in this stream: a leaf of 15 instances cannot be told from one
     for (int64_t i = 0; i < nT; i++) if (((unsigned)__builtin_bit_cast(int, out.tlas[(size_t)i].hi.w) >> 28) > 14u) leavesFit = false;
-    if (out.ok && out.feat == 0 && reachableT > 0 && nT + nTI < kEnd && leavesFit && !HRT_ENV("HRT_NO_INLINE_INSTANCES"))
+    if (out.ok && out.feat == 0 && reachableT > 0 && nT + nTI < kEnd && leavesFit)
     {
         std::vector<int32_t> nidx((size_t)nT);
         int32_t at = 0;
@@ -1063,7 +1059,7 @@ std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
     {
         const NodeQ& q = out.tlas[(size_t)i];
         const int cnt = (int)((unsigned)__builtin_bit_cast(int, q.hi.w) >> 28), first = __builtin_bit_cast(int, q.lo.w);
-        if (cnt == 0 || !(reachableT < 0 || (int32_t)i < reachableT)) continue;
+        if (cnt == 0 || (int32_t)i >= reachableT) continue;
         for (int j = 0; j < cnt; j++)
         {
             if ((int64_t)first + j < 0 || (int64_t)first + j >= nTI) { out.nested = false; break; }
@@ -1209,7 +1205,7 @@ TlQueues tl_queues(const DeviceState& d, int lane, int kind, long long cap)
 #ifndef HRT_TL_ROUNDS
 #define HRT_TL_ROUNDS 3
 #endif
-// One walk launch of the streamed pipeline through the treelet walker: fresh rays, kTlRounds rounds over the binned rays, clean-up.
+// One walk launch of the streamed pipeline through the treelet walker: fresh rays, HRT_TL_ROUNDS rounds over the binned rays, clean-up.
 template <int F, bool ANY, bool EXISTS, int LT>
 int launch_tl_walk(hrt_ctx* c, DeviceState& d, const TracerPackedT<F>& tr, const WfBuffers& W, int lane, long long cap, int depth, hipStream_t st, dim3 gridW, dim3 gridR)
 {
@@ -1217,13 +1213,12 @@ int launch_tl_walk(hrt_ctx* c, DeviceState& d, const TracerPackedT<F>& tr, const
     const TlQueues Q = tl_queues(d, lane, ANY ? 0 : 1, cap);
     const int histBins = T.nTl <= kTlHistLds ? T.nTl : 0;
     const size_t lds0 = tl_shared_bytes(0, T.redLds, histBins), lds1 = tl_shared_bytes(T.tlBytesMax, T.redLds, histBins);
-    static const int rounds = HRT_ENV("HRT_TL_ROUNDS") ? std::max(0, atoi(HRT_ENV("HRT_TL_ROUNDS"))) : HRT_TL_ROUNDS;
     if (lds1 > 65536) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&hrt_tl_walk_kernel<F, ANY, EXISTS, LT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     const dim3 block(256), grid1((unsigned)(d.n_cu * 8));
     HIPCHK(c, hipMemsetAsync(Q.hist, 0, ((size_t)T.nTl + 32) * sizeof(int), st));
     const int* cnt = (ANY ? W.cntS : W.cntA) + (size_t)depth * W.nRanges;
     hipLaunchKernelGGL((hrt_tl_walk_kernel<F, ANY, EXISTS, LT, 0>), gridW, block, lds0, st, tr, T, Q, W, depth, histBins, 0, 0);
-    for (int r = 0; r < rounds; r++)
+    for (int r = 0; r < HRT_TL_ROUNDS; r++)
     {
         hipLaunchKernelGGL(hrt_tl_scan_kernel, dim3(1), dim3(1024), 0, st, Q, T.nTl);
         hipLaunchKernelGGL(hrt_tl_scatter_kernel, gridR, block, 0, st, Q, T.nTl, cnt, W.nRanges);
@@ -1249,15 +1244,11 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
         // frames without ReSTIR reuse: the leaf-sweep tracer's kernels with the import code compiled out (hrt_device.hpp, REUSE)
         const bool noReuse = std::is_same<TR, TracerFlat>::value && !count && k.enableTemporal == 0 && k.enableSpatial == 0;
         // sample groups when the tile gives the machine less than ~5 rounds of waves
-        static const int splitEnv = HRT_ENV("HRT_SPLIT") ? atoi(HRT_ENV("HRT_SPLIT")) : -1;          // A/B knob: 0 never, n > 0 force n groups
         const int sppN = k.spp > 1 ? k.spp : 1;
         const long long waves = (long long)tm.nTiles * tm.wpb, slots = (long long)d.n_cu * 4 * HRT_PT_WAVES;
         int nGroups = 1;
-        if (!count && k.maxDepth <= 64 && sppN > 1 && waves > 0)
-        {
-            if (splitEnv > 0) nGroups = std::min(splitEnv, sppN);
-            else if (splitEnv < 0 && waves < 5 * slots) nGroups = (int)std::min<long long>(std::min(sppN, 8), (16 * slots + waves - 1) / waves);   // config 2 over N = 2 / 4 / 8 ranks: 4 groups each (1.111 -> 1.079, 0.593 -> 0.555, 0.296 ms)
-        }
+        if (!count && k.maxDepth <= 64 && sppN > 1 && waves > 0 && waves < 5 * slots)
+            nGroups = (int)std::min<long long>(std::min(sppN, 8), (16 * slots + waves - 1) / waves);   // config 2 over N = 2 / 4 / 8 ranks: 4 groups each (1.111 -> 1.079, 0.593 -> 0.555, 0.296 ms)
         if (nGroups > 1)
         {
             const int perGroup = (sppN + nGroups - 1) / nGroups;
@@ -1299,9 +1290,6 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     // shade / finish / resolve kernels of the other fill them (measured first as two processes sharing the card: configs 4 / 5
     // -11 % / -7 %).  A frame that fits one batch is cut into two halves; only the ordered steps -- the per-pixel sample sum
     // and the last-writer reservoir in wf_resolve -- are chained by events, in batch order.
-#ifdef HRT_ONE_BATCH_LANE          // A/B
-    const int nLanes = 1;
-#else
     // ... a frame that fits one batch is cut in two only while each half still fills the machine (measured: halves of 16.6 M paths
     // config 3 -5.5 %, config 4 +-0; halves of 8.3 M paths config 5 +13 %)
     constexpr long long kMinHalfBatchPaths = 12000000;
@@ -1309,7 +1297,6 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     const bool halves = !severalBatches && spp >= 2 && (long long)((spp + 1) / 2) * g.nOrd >= kMinHalfBatchPaths;
     const int nBatchesNatural = (int)((spp + sb - 1) / sb);
     const int nLanes = severalBatches ? std::min(kBatchLanes, nBatchesNatural) : (halves ? std::min(kBatchLanes, 2) : 1);
-#endif
     if (nLanes >= 2 && !severalBatches && sb > (spp + 1) / 2) sb = (spp + 1) / 2;
     const long long batchPaths = sb * (long long)g.nOrd;
     const int nRanges = (int)((batchPaths + kRange - 1) / kRange);
@@ -1327,14 +1314,11 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     const dim3 block(256), gridR((nRanges + 3) / 4), gridP((g.nOrd + 255) / 256);
     // walk launches are persistent: enough workgroups to fill every wave slot, each wave pulls ranges until none is left
     const dim3 gridW((unsigned)std::min<long long>((nRanges + 3) / 4, (long long)d.n_cu * (nLanes >= 2 ? kWalkBlocksPerCU2 : kWalkBlocksPerCU)));
-    static const bool forkShadow = HRT_ENV("HRT_NO_FORK") == nullptr;       // A/B knob
-    static const bool forkStatic = HRT_ENV("HRT_FORK_STATIC") != nullptr;   // A/B knob
     // finish of a bounce and shade of the next one as ONE kernel (the vertex never round-trips through its 22 planes): sphere-instance scenes
     // (config 3: path stage -3.6 %, HBM traffic 13.6 -> 11.7 GB per frame).  Triangle scenes keep the two kernels: their walks leave the vector
     // units to the other sample batch's shade / finish kernels, and the fused kernel (111 registers through the fetch-bound half) fills them
     // worse (config 5 +3 %, config 4 +-0.5 %: profiles/EXPERIMENTS.md)
-    static const int fuseEnv = HRT_ENV("HRT_FUSE") ? atoi(HRT_ENV("HRT_FUSE")) : -1;       // A/B knob
-    const bool fuse = PackedFeat<TR>::value >= 0 && (fuseEnv >= 0 ? fuseEnv != 0 : PackedFeat<TR>::value == 0);
+    constexpr bool fuse = PackedFeat<TR>::value == 0;
     for (int j = 0; j < nLanes; j++) Wl[j].pingpong = fuse ? 1 : 0;
     int batch = 0;
     for (int b0 = 0; b0 < spp; b0 += (int)sb, batch++)
@@ -1349,12 +1333,8 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
         for (int depth = 0; depth < k.maxDepth; depth++)
         {
             const int vsel = depth & 1;
-#ifdef HRT_NO_EXISTS            // A/B
-            const bool lastBounce = false;
-#else
             const bool lastBounce = depth + 1 >= k.maxDepth;        // its closest-hit walk only decides hit or miss
-#endif
-            const int chained = (PackedFeat<TR>::value > 0 || HRT_CHAIN_FEAT0) ? 1 : 0;
+            constexpr int chained = PackedFeat<TR>::value > 0 ? 1 : 0;
             if (depth == 0)
             {
                 if (count) hipLaunchKernelGGL((hrt_wf_shade_kernel<true, true>), gridR, block, 0, sMain, k, g, d.gb, resPrev, nPix, W, vsel, depth, cnt1);
@@ -1397,12 +1377,6 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
                 bool second = false;
                 TR trFin = tr;
                 if constexpr (F == 0) { second = d.any_ok && !count; if (second) trFin.P = d.dpackedAny; }
-#ifdef HRT_NO_ALT_CLOSEST        // A/B: closest-hit walks of the inner bounces on the uploaded tree
-                const bool secondClosest = false;
-                trFin = tr;
-#else
-                const bool secondClosest = second;
-#endif
                 auto launch_closest = [&](hipStream_t st) {
                     if constexpr (F != 0)
                         if (useTl)
@@ -1416,7 +1390,7 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
                             return;
                         }
                     if constexpr (F == 0)
-                        if (lastBounce ? d.any_ok : secondClosest)
+                        if (lastBounce ? d.any_ok : second)
                         {
                             TR trAny = tr; trAny.P = d.dpackedAny;
                             if (lastBounce) hipLaunchKernelGGL((hrt_wf_walk_closest_kernel<F, false, true, true>), chained ? gridW : gridR, block, 0, st, trAny, tr, W, depth, chained, cnt1);
@@ -1433,16 +1407,17 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
                     if (lt3) hipLaunchKernelGGL((hrt_wf_walk_closest_kernel<F, false, true, false, (F != 0 ? 3 : 2)>), chained ? gridW : gridR, block, 0, st, tr, tr, W, depth, chained, cnt1);
                     else     hipLaunchKernelGGL((hrt_wf_walk_closest_kernel<F, false, true>), chained ? gridW : gridR, block, 0, st, tr, tr, W, depth, chained, cnt1);
                 };
-                // the winners' shading: on the last bounce the paths end (wf_finish); before it the next vertex is shaded in the same kernel
-                const bool finalBounce = depth + 1 >= k.maxDepth;
+                // the winners' shading: on the last bounce the paths end (wf_finish); before it the fused kernel shades the next vertex
                 auto launch_finish = [&](const TR& trF) {
-                    if (count)
-                    {
-                        if (finalBounce || !fuse) hipLaunchKernelGGL((hrt_wf_finish_kernel<F, true>), gridR, block, 0, sMain, trF, k, W, vsel, depth);
-                        else hipLaunchKernelGGL((hrt_wf_finish_shade_kernel<F, true>), gridR, block, 0, sMain, trF, k, g, d.gb, resPrev, nPix, W, vsel, depth, cnt1);
-                    }
-                    else if (finalBounce || !fuse) hipLaunchKernelGGL((hrt_wf_finish_kernel<F, false>), gridR, block, 0, sMain, trF, k, W, vsel, depth);
-                    else hipLaunchKernelGGL((hrt_wf_finish_shade_kernel<F, false>), gridR, block, 0, sMain, trF, k, g, d.gb, resPrev, nPix, W, vsel, depth, cnt1);
+                    if constexpr (fuse)
+                        if (!lastBounce)
+                        {
+                            if (count) hipLaunchKernelGGL((hrt_wf_finish_shade_kernel<F, true>), gridR, block, 0, sMain, trF, k, g, d.gb, resPrev, nPix, W, vsel, depth, cnt1);
+                            else       hipLaunchKernelGGL((hrt_wf_finish_shade_kernel<F, false>), gridR, block, 0, sMain, trF, k, g, d.gb, resPrev, nPix, W, vsel, depth, cnt1);
+                            return;
+                        }
+                    if (count) hipLaunchKernelGGL((hrt_wf_finish_kernel<F, true>), gridR, block, 0, sMain, trF, k, W, vsel, depth);
+                    else       hipLaunchKernelGGL((hrt_wf_finish_kernel<F, false>), gridR, block, 0, sMain, trF, k, W, vsel, depth);
                 };
                 if (count)
                 {
@@ -1450,7 +1425,7 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
                     hipLaunchKernelGGL((hrt_wf_walk_closest_kernel<F, true>), chained ? gridW : gridR, block, 0, sMain, tr, tr, W, depth, chained, cnt1);
                     launch_finish(tr);
                 }
-                else if ((chained || forkStatic) && forkShadow)
+                else if (chained)
                 {   // the two walks of a bounce are independent (shadow requests vs bounce rays) and both are persistent
                     // launches that end in a drain: on two streams the second one's workgroups move into the wave slots
                     // the first one's drain frees, instead of waiting for its last ray
@@ -1666,9 +1641,7 @@ extern "C" {
 
 const char* hrt_version(void)
 {
-#if defined(HRT_TUNING)
-    return "hip_raytrace 0.4 (gfx950) tuning-build";
-#elif defined(HRT_TEST_HOOKS)
+#if defined(HRT_TEST_HOOKS)
     return "hip_raytrace 0.4 (gfx950) test-hooks";
 #else
     return "hip_raytrace 0.4 (gfx950)";
@@ -1851,8 +1824,6 @@ try {
     emptyTlas.left = emptyTlas.right = emptyTlas.first = emptyTlas.skipIndex = -1;   // an empty TLAS ends the walk at once
     // topology of the second tree (many-sphere scenes): a function of the instances alone, computed once for all devices
     SahTopology sahOnce; bool haveSah = false;
-#ifndef HRT_NO_HOST_SAH
-#ifndef HRT_NO_ANY_TREE
     if (ph.ok && ph.feat == 0 && s->n_instances >= kAnyTreeMinInstances && ph.n_tlasX > 0 && ph.inst_once && s->n_tlasInstanceIndices == s->n_instances &&
         ph.own_in_world && s->n_instances <= kHostSahMaxInstances && s->n_instances > 2)
     {
@@ -1860,8 +1831,6 @@ try {
         host_sah_topology(inst, sahOnce);
         haveSah = true;
     }
-#endif
-#endif
     TreeletsHost tlh;
     if (ph.ok && (ph.feat & 1) && ph.blas_refit_ok && !ph.meshRanges.empty()) build_treelets(ph.blas, ph.bsubend, ph.meshRanges, g_treelet_limits, tlh);
     for (DeviceState& d : c->dev)
@@ -1917,7 +1886,7 @@ try {
             T.tlas = (NodeQ*)d.packed[0]; T.finst = (FInst*)d.packed[1]; T.tlasX = (NodeQ*)d.packed[6]; T.flat = (NodeQ*)d.packed[4];
             T.parent = (int*)d.tlaux[0]; T.nchild = (int*)d.tlaux[1]; T.arrive = (int*)d.tlaux[2]; T.scanIn = (unsigned long long*)d.tlaux[3]; T.scanOut = (unsigned long long*)d.tlaux[4];
             T.scanTmp = d.tlaux[9]; T.scanTmpBytes = scanTmp; T.costPartial = (float*)((char*)d.tlaux[9] + scanTmp);
-            T.directMax = (ph.refit_ok && !HRT_ENV("HRT_BUILDER_ORDER")) ? 63 : 1;
+            T.directMax = 63;                                   // walk order; apply_update rebuilds a tree that fails refit_ok first
             T.sa = (float*)d.tlaux[5]; T.flags = (int*)d.tlaux[6]; T.cost = (float*)d.tlaux[7]; T.saBase = (float*)d.tlaux[8];
             T.nI = (int)s->n_instances; T.nT = (int)s->n_tlasNodes; T.nTI = (int)s->n_tlasInstanceIndices;
             if ((!ph.meshInst.empty() || !ph.sphereInst.empty()) && ph.blas_refit_ok)
@@ -2203,9 +2172,6 @@ bool reorder_second_tree(const std::vector<NodeQ>& X, const int sign[3], int bas
 int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, int64_t nSlots, bool instOnce, const SahTopology* pre, const hrt_instance* hostInst)
 {
     d.any_ok = false; d.any_built = false;
-#ifdef HRT_NO_ANY_TREE             // A/B
-    return HRT_OK;
-#endif
     // own_in_world: the second tree's leaf boxes are unions of the instances' worldBounds, and its exactness argument needs every instance's
     // own box inside them (an instance whose BLAS the position-indexed builder put over another sphere, Scene.cs:386-395, breaks that)
     if (!c->packed_ok || c->packed_feat != 0 || c->n_inst < kAnyTreeMinInstances || !d.dpacked.tlasX || !instOnce || nSlots != c->n_inst || !c->own_in_world) return HRT_OK;
@@ -2234,7 +2200,6 @@ int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, 
         inst.resize((size_t)c->n_inst);
         HIPCHK(c, hipMemcpy(inst.data(), T.instances, inst.size() * sizeof(hrt_instance), hipMemcpyDeviceToHost));
     }
-#ifndef HRT_NO_HOST_SAH            // A/B
     if (c->n_inst <= kHostSahMaxInstances && c->n_inst > 2)
     {
         // the topology depends on the instances alone: the upload computes it once and hands it to every device
@@ -2250,8 +2215,7 @@ int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, 
         HIPCHK(c, hipStreamSynchronize(d.stream));              // the vectors go out of scope
     }
     else
-#endif
-    HIPCHK(c, tlas_rebuild_topology(T, d.stream, &leaves));
+        HIPCHK(c, tlas_rebuild_topology(T, d.stream, &leaves));
     T.directMax = 63;                                           // emitted in walk order
     HIPCHK(c, tlas_finish(T, d.stream));
     HIPCHK(c, tlas_inflate(T, d.stream));
@@ -2283,7 +2247,6 @@ int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, 
     if (d.tl2mem[17]) { (void)hipFree(d.tl2mem[17]); d.tl2mem[17] = nullptr; }
     HIPCHK(c, hipMalloc(&d.tl2mem[17], (size_t)nSlots * 4));
     if (d.tl2mem[15]) { (void)hipFree(d.tl2mem[15]); d.tl2mem[15] = nullptr; }
-#ifndef HRT_NO_ORDERED_COPIES      // A/B
     // Which signs select a numbering: the two axes along which the instances are spread most (extent of the box centres between their
     // 5th and 95th percentile: one huge ground sphere must not count) -- measured on config 3 (22 k records, 0.7 MB a copy), every walk
     // ordered: x and z 16.2 ms, z 16.8, x 16.7, all three 18.1, none 17.5, y alone 18.9 (along y the builder's order, ground first, is the
@@ -2351,7 +2314,6 @@ int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, 
             d.ordX = all.size(); d.ordP = allP.size();
         }
     }
-#endif
     d.any_ok = true; d.any_built = true;
     return HRT_OK;
 }
@@ -2462,8 +2424,7 @@ int apply_update(hrt_ctx* c, int policy, const char* who, const std::function<in
         // the walkers' view of the tree
         const bool general = h_flags[0] != 0;
         d.dpacked.nTlas = T.nT;
-        const bool walkOrder = action == HRT_REBUILD_FORCE_REBUILD || c->tlas_on_device || !HRT_ENV("HRT_BUILDER_ORDER");
-        const bool inl = !general && !c->feat_alpha && walkOrder && (int64_t)T.nT + T.nTI < kEnd && !HRT_ENV("HRT_NO_INLINE_INSTANCES");
+        const bool inl = !general && !c->feat_alpha && (int64_t)T.nT + T.nTI < kEnd;
         d.dpacked.tlasX = inl ? (const NodeQ*)d.packed[6] : nullptr;
         d.dpacked.nTlasX = inl ? T.nT + T.nTI : 0;
         // the second tree follows the scene (same topology, new boxes) or stands down
@@ -2479,7 +2440,7 @@ int apply_update(hrt_ctx* c, int policy, const char* who, const std::function<in
             // the leaf sweep skips box tests the reference makes, which is only sound over nested boxes: the device's trees are unions of
             // the instances' worldBounds, so it takes every fast-sphere instance's own box to lie inside its worldBounds
             // ... and every worldBounds to be a regular box (no NaN bound, min <= max: h_flags[1]), or the unions are not nested
-            c->flat_leaves = (!general && !c->feat_alpha && walkOrder && c->own_in_world && h_flags[1] == 0 && c->tlas_leaves > 0 && c->tlas_leaves <= kFlatMaxLeaves) ? c->tlas_leaves : 0;
+            c->flat_leaves = (!general && !c->feat_alpha && c->own_in_world && h_flags[1] == 0 && c->tlas_leaves > 0 && c->tlas_leaves <= kFlatMaxLeaves) ? c->tlas_leaves : 0;
             c->n_tlas = T.nT; c->n_slots = T.nTI;
             c->small_scene = (c->n_tlas + c->n_blas) <= kSmallSceneNodes;
             c->tlas_on_device = true;
@@ -2731,9 +2692,9 @@ try {
         k.rngLockNoise = p->rngLockNoise; k.spp = p->spp; k.maxDepth = p->maxDepth;
         return k;
     };
-    // pixel kernels: waves per workgroup.  One wave per workgroup gives the dispatcher the finest grain: the launch ends when
-    // the last 8x8 tile ends instead of the last 32x8 tile (matters most when a rank renders 1/8 of the image)
-    static const int ptWaves = HRT_ENV("HRT_PT_BLOCK") ? std::max(1, std::min(4, atoi(HRT_ENV("HRT_PT_BLOCK")) / 64)) : 4;
+    // pixel kernels: four waves per workgroup, each on an 8x8 tile, side by side (a 32x8 tile: the 256 lanes of the path-trace
+    // kernels' launch bounds)
+    constexpr int ptWaves = 4;
     auto tile_map = [&](const DeviceState& d) {
         TileMap tm;
         tm.wpb = ptWaves;
@@ -2747,8 +2708,7 @@ try {
     const int variant = usePacked ? c->packed_feat : -1;
     const bool mega = (flags & HRT_FLAG_MEGAKERNEL) ? true : ((flags & HRT_FLAG_STREAMED) ? false : c->small_scene);
     // production frames of a tiny fast-sphere scene in the fused kernel: wave-uniform sweep over the TLAS leaves
-    static const bool noFlat = HRT_ENV("HRT_NO_FLAT") != nullptr;       // A/B knob
-    const bool flat = variant == 0 && mega && !count && c->flat_leaves > 0 && !noFlat;
+    const bool flat = variant == 0 && mega && !count && c->flat_leaves > 0;
     auto with_tracer = [&](DeviceState& d, auto fn) -> int {
         if (flat) { TracerFlat t; t.tree.P = d.dpacked; t.tree.S = d.dscene; t.leaves = (const NodeQ*)d.packed[4]; t.nLeaves = c->flat_leaves; return fn(t); }
         if (variant == 0)      { TracerPackedT<0> t; t.P = d.dpacked; t.S = d.dscene; return fn(t); }

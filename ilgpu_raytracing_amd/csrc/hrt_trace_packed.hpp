@@ -319,13 +319,11 @@ struct TracerPackedT {
         bool anom = false;          // TIES: the current winner's own slab entry exceeds its hit distance
         int cur = 0;
         const NodeQ* nodes = P.tlas;
-#ifndef HRT_NO_ORDERED_PRIMARY     // A/B
         if (TIES && P.tlasO != nullptr)     // the second tree in the numbering of this ray's direction (DPacked::tlasXO): near child first
         {
             nodes = P.tlasO;
             cur = ord_copy(P.xAxes, wray.d.x, wray.d.y, wray.d.z) * P.oStride;
         }
-#endif
         for (;;)
         {
             int lfirst = 0, lcount = 0, lskip = kEnd;
