@@ -88,9 +88,55 @@ HRT_D F3 normalize(F3 v)   // Float3.cs:91-95
     float inv = rsqrt_clamped<FINITE>(hrt_fmax(1e-20f, v.x * v.x + v.y * v.y + v.z * v.z));
     return mk3(v.x * inv, v.y * inv, v.z * inv);
 }
+// The short divide forms below are hipcc's sequence for n / d (-fhip-fp32-correctly-rounded-divide-sqrt): n' = v_div_scale(n),
+// d' = v_div_scale(d), r0 = v_rcp(d'), r1 = fma(fma(-d', r0, 1), r0, r0), q0 = n' r1, q1 = fma(fma(-d', q0, n'), r1, q0),
+// v_div_fmas(fma(-d', q1, n'), r1, q1), v_div_fixup -- minus v_div_scale, v_div_fmas and v_div_fixup.  v_div_scale leaves both
+// operands alone and clears VCC (so v_div_fmas is a plain fma) when d and n / d are normal, 1 / d is not denormal, n != 0, the
+// biased exponent of n is > 23 and exp(n) - exp(d) < 96; v_div_fixup returns its input unchanged for finite nonzero normal
+// operands and a normal quotient.  Where exp(n) - exp(d) >= 96, hipcc scales d by 2^64 and the quotient back by 2^64: every
+// intermediate of both forms stays normal, v_rcp depends on the mantissa only, so the unscaled form gives the same bits.
+
+// 1 / x, IEEE, for 2^-94 <= |x| <= 2^125: no operand is scaled, the quotient is normal (numerator 1: n * r1 == r1).
+// 7 instructions instead of 11; tests/test_math_short_div_gpu.py compares it with 1.0f / x for every float in the domain.
+HRT_D bool rcp_domain(float x) { return __builtin_fabsf(x) >= 0x1p-94f && __builtin_fabsf(x) <= 0x1p125f; }
+HRT_D float rcp_normal_range(float x)
+{
+    const float r0 = __builtin_amdgcn_rcpf(x);
+    const float e0 = __builtin_fmaf(-x, r0, 1.f);
+    const float r1 = __builtin_fmaf(e0, r0, r0);
+    const float e1 = __builtin_fmaf(-x, r1, 1.f);
+    const float q1 = __builtin_fmaf(e1, r1, r1);
+    const float e2 = __builtin_fmaf(-x, q1, 1.f);
+    return __builtin_fmaf(e2, r1, q1);
+}
+// n / d by the refined reciprocal r1 of d, which depends on d only: a ray computes it once for every sphere it tests.
+// Domain 1 <= |d| < 4 (a ray direction of |dir|^2 in [0.5, 2): every normalised one) and every finite n with |n| >= 2^-100
+// (exp(n) - exp(d) >= 96 only for |n| >= 2^96: the scaling case above).  Outside it, for |n| < 2^-100 the result has
+// |q| < 2^-98 like n / d, and for n = +-inf or NaN it is NaN.  5 instructions instead of 11, no v_rcp; the tests compare
+// it with n / d for every n over a dense set of d and for 2^34 random pairs.
+struct Recip { float d, r; };
+HRT_D bool recip_domain(float d) { return __builtin_fabsf(d) >= 1.f && __builtin_fabsf(d) < 4.f; }
+HRT_D Recip recip_of(float d)
+{
+    const float r0 = __builtin_amdgcn_rcpf(d);
+    Recip R; R.d = d; R.r = __builtin_fmaf(__builtin_fmaf(-d, r0, 1.f), r0, r0);
+    return R;
+}
+HRT_D float div_by(float n, Recip R)
+{
+    const float q0 = n * R.r;
+    const float q1 = __builtin_fmaf(__builtin_fmaf(-R.d, q0, n), R.r, q0);
+    return __builtin_fmaf(__builtin_fmaf(-R.d, q1, n), R.r, q1);
+}
+HRT_D float div_by(float n, float d) { return n / d; }
+
 HRT_D F3 inv_dir(F3 d)     // RTRay.cs:548-549
 {
-    return mk3(1.f / (d.x != 0.f ? d.x : 1e-8f), 1.f / (d.y != 0.f ? d.y : 1e-8f), 1.f / (d.z != 0.f ? d.z : 1e-8f));
+    const float x = d.x != 0.f ? d.x : 1e-8f, y = d.y != 0.f ? d.y : 1e-8f, z = d.z != 0.f ? d.z : 1e-8f;
+    // wave-uniform: a wave with any component outside rcp_domain (denormal, tiny, huge, NaN) takes the IEEE sequence
+    if (__builtin_amdgcn_ballot_w64(!(rcp_domain(x) && rcp_domain(y) && rcp_domain(z))) == 0)
+        return mk3(rcp_normal_range(x), rcp_normal_range(y), rcp_normal_range(z));
+    return mk3(1.f / x, 1.f / y, 1.f / z);
 }
 
 struct Ray { F3 o, d, inv; };
@@ -242,8 +288,15 @@ HRT_D bool hit_aabb(const Ray& r, const hrt_bvh_node* n, float tMin, float tMax)
 }
 
 // SceneDeviceViews.cs:517-533 without the normal (:534-535 is a pure function of t: deferred)
-// a = dot(r.d, r.d) is a property of the ray: callers that test several spheres with one ray compute it once
-HRT_D bool hit_sphere_ta(const Ray& r, float a, F3 c, float radius, float& t)
+// a = dot(r.d, r.d) is a property of the ray: callers that test several spheres with one ray compute it once, and twoA = 2 a
+// as a float (IEEE divide) or, for a ray in recip_domain(2 a), as its Recip.  Both return the same hit.  The quotients are
+// (-b -+ sq) / 2a: where |-b -+ sq| >= 2^-100 and finite, div_by gives the same bits; below, both quotients are < 0.001 and
+// rejected alike; a non-finite numerator gives IEEE +-inf or NaN and div_by NaN, and no caller accepts either (+inf fails
+// t < limit, NaN fails t > 0.001; after a first root of -inf the second one is -b + sq with b >= 2^127 > sq, or +inf, or NaN).
+// sq: disc is >= 0 or NaN here; sqrt_normal_range is exact for +0, +inf and disc >= 2^-96 and gives NaN for NaN, and a wave with
+// a lane in (0, 2^-96) takes hrt_sqrt.
+template <class D>
+HRT_D bool hit_sphere_q(const Ray& r, float a, D twoA, F3 c, float radius, float& t)
 {
     F3 oc = r.o - c;
     float b = 2.f * dot(oc, r.d);
@@ -251,16 +304,17 @@ HRT_D bool hit_sphere_ta(const Ray& r, float a, F3 c, float radius, float& t)
     float disc = b * b - 4.f * a * cc;
     if (disc < 0.f) return false;
     PSTAT(9);
-    float sq = hrt_sqrt(disc);
-    float tt = (-b - sq) / (2.f * a);
+    float sq = __builtin_amdgcn_ballot_w64(disc > 0.f && disc < 0x1p-96f) ? hrt_sqrt(disc) : sqrt_normal_range(disc);
+    float tt = div_by(-b - sq, twoA);
     if (tt < 0.001f) {
         PSTAT(10);
-        tt = (-b + sq) / (2.f * a);
+        tt = div_by(-b + sq, twoA);
         if (tt < 0.001f) return false;
     }
     t = tt;
     return true;
 }
+HRT_D bool hit_sphere_ta(const Ray& r, float a, F3 c, float radius, float& t) { return hit_sphere_q(r, a, 2.f * a, c, radius, t); }
 HRT_D bool hit_sphere_t(const Ray& r, F3 c, float radius, float& t) { return hit_sphere_ta(r, dot(r.d, r.d), c, radius, t); }
 HRT_D F3 sphere_normal(const Ray& r, F3 c, float t) { return normalize((r.o + r.d * t) - c); }   // :534-535
 

@@ -389,23 +389,74 @@ __global__ void hrt_math_probe_kernel(int fn, int n, const float* x, const float
     case 25: { float s, c; hrt_sincos_nonneg(a, &s, &c); r = c; } break;
     case 26: r = sqrt_normal_range<true>(a); break;
     case 27: r = rsqrt_clamped<true>(a); break;
+    case 28: r = rcp_normal_range(a); break;
+    case 29: r = div_by(a, recip_of(b)); break;
+    case 30: r = inv_dir(mk3(a, b, 0.5f)).x; break;             // guarded: a wave with a out of rcp_domain takes 1.0f / a
+    case 31: {                                                  // TracerFlat's sphere step: Recip or IEEE divide by a ballot on 2a
+        Ray ray; ray.o = mk3(0.f, 0.f, 0.f); ray.d = mk3(0.f, 0.f, b); ray.inv = ray.d;
+        const float sa = dot(ray.d, ray.d);
+        const F3 c = mk3(0.25f, 0.f, a);
+        float t = -1.f;
+        const bool h = __builtin_amdgcn_ballot_w64(!recip_domain(2.f * sa)) == 0 ? hit_sphere_q(ray, sa, recip_of(2.f * sa), c, 1.f, t)
+                                                                                  : hit_sphere_q(ray, sa, 2.f * sa, c, 1.f, t);
+        r = h ? t : -1.f;
+    } break;
     }
     out[i] = r;
 }
 
 // exhaustive device-side comparison of a trimmed function with its IEEE definition over every float of its domain:
-// which 0: rsqrt_clamped(x) vs hrt_rsqrt(x) for x in [1e-20, +inf]; 1: sqrt_normal_range(x) vs hrt_sqrt(x) for x = +0, x in [2^-96, +inf]
+// which 0: rsqrt_clamped(x) vs hrt_rsqrt(x) for x in [1e-20, +inf]; 1: sqrt_normal_range(x) vs hrt_sqrt(x) for x = +0, x in [2^-96, +inf];
+// 2: rcp_normal_range(x) vs 1.0f / x for every x in rcp_domain (both signs);
+// 3: div_by(n, recip_of(d)) vs n / d for EVERY float n and 1028 denominators d in [1, 4): each 2^14-th float from 1.0 and the
+//    neighbours of 1, 2 and 4;  4: the same for 2^34 hashed pairs (n any float, d any float in [1, 4)).
+// For 3 and 4 a pair counts as a mismatch unless the bits agree (|n| >= 2^-100, finite), |div_by| < 2^-98 (|n| < 2^-100) or
+// div_by is NaN (n infinite or NaN): the contract of div_by (hrt_device.hpp).
+HRT_D bool div_by_ok(float n, float d)
+{
+    const float a = div_by(n, recip_of(d)), b = n / d;
+    if (!hrt_isfinite(n)) return a != a;
+    if (__builtin_fabsf(n) < 0x1p-100f) return __builtin_fabsf(a) < 0x1p-98f;
+    return __float_as_uint(a) == __float_as_uint(b);
+}
+HRT_D float dense_denominator(int j)
+{
+    const unsigned edges[4] = {0x3F800001u, 0x3FFFFFFFu, 0x40000001u, 0x407FFFFFu};
+    return __uint_as_float(j < 1024 ? 0x3F800000u + (unsigned)j * 0x4000u : edges[j - 1024]);
+}
 __global__ void hrt_math_exhaustive_kernel(int which, unsigned long long* mismatches, unsigned* firstBad)
 {
-    const unsigned lo = which == 0 ? __float_as_uint(1e-20f) : __float_as_uint(0x1p-96f);
-    const unsigned hi = 0x7F800000u;                              // +inf, inclusive
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, first = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;
     unsigned long long bad = 0;
-    for (unsigned long long u = (unsigned long long)lo + blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; u <= hi; u += (unsigned long long)gridDim.x * blockDim.x)
+    if (which <= 2)
     {
-        const float x = __uint_as_float((unsigned)u);
-        const float a = which == 0 ? rsqrt_clamped(x) : sqrt_normal_range(x);
-        const float b = which == 0 ? hrt_rsqrt(x) : hrt_sqrt(x);
-        if (__float_as_uint(a) != __float_as_uint(b)) { bad++; atomicMin(firstBad, (unsigned)u); }
+        const unsigned lo = which == 0 ? __float_as_uint(1e-20f) : which == 1 ? __float_as_uint(0x1p-96f) : __float_as_uint(0x1p-94f);
+        const unsigned hi = which == 2 ? __float_as_uint(0x1p125f) : 0x7F800000u;            // inclusive
+        const int signs = which == 2 ? 2 : 1;
+        for (int sgn = 0; sgn < signs; sgn++)
+            for (unsigned long long u = (unsigned long long)lo + first; u <= hi; u += stride)
+            {
+                const unsigned bits = (unsigned)u | (sgn ? 0x80000000u : 0u);
+                const float x = __uint_as_float(bits);
+                const float a = which == 0 ? rsqrt_clamped(x) : which == 1 ? sqrt_normal_range(x) : rcp_normal_range(x);
+                const float b = which == 0 ? hrt_rsqrt(x) : which == 1 ? hrt_sqrt(x) : 1.0f / x;
+                if (__float_as_uint(a) != __float_as_uint(b)) { bad++; atomicMin(firstBad, bits); }
+            }
+    }
+    else if (which == 3)
+    {
+        for (unsigned long long u = first; u <= 0xFFFFFFFFull; u += stride)
+            for (int j = 0; j < 1028; j++)
+                if (!div_by_ok(__uint_as_float((unsigned)u), dense_denominator(j))) { bad++; atomicMin(firstBad, (unsigned)u); }
+    }
+    else
+    {
+        for (unsigned long long i = first; i < (1ull << 34); i += stride)
+        {
+            const unsigned hn = hash32((unsigned)i ^ hash32((unsigned)(i >> 32) + 0x9E3779B9u)), hd = hash32(hn ^ 0x85EBCA6Bu);
+            const float d = __uint_as_float(0x3F800000u + hd % 0x01000000u);                  // [1, 4): 2^24 floats
+            if (!div_by_ok(__uint_as_float(hn), d)) { bad++; atomicMin(firstBad, hn); }
+        }
     }
     if (which == 1 && blockIdx.x == 0 && threadIdx.x == 0 && __float_as_uint(sqrt_normal_range(0.f)) != 0u) bad++;
     if (bad) atomicAdd(mismatches, bad);
@@ -3067,10 +3118,10 @@ try {
 catch (...) { return on_exception(c, "hrt_math_probe"); }
 
 // test hook: compares a trimmed device function with its IEEE definition over EVERY float of its stated domain, on the device
-// (which: 0 rsqrt_clamped, 1 sqrt_normal_range); *mismatches = number of differing bit patterns, *first_bad = the smallest one
+// (which: 0 rsqrt_clamped, 1 sqrt_normal_range, 2 rcp_normal_range, 3 and 4 div_by); *mismatches = number of differing bit patterns, *first_bad = the smallest one
 int hrt_math_exhaustive(hrt_ctx* c, int which, uint64_t* mismatches, uint32_t* first_bad)
 try {
-    if (!c || !mismatches || which < 0 || which > 1) return HRT_ERR_INVALID_ARG;
+    if (!c || !mismatches || which < 0 || which > 4) return HRT_ERR_INVALID_ARG;
     DeviceState& d = c->dev[0];
     HIPCHK(c, hipSetDevice(d.device_id));
     unsigned long long* dm = nullptr;

@@ -662,6 +662,15 @@ struct TracerFlat {
         if (COUNT || !finite_ray(wray)) return tree.template closest<COUNT>(wray, best, C);
         float bestT = 1e30f; int bestSlot = -1, bestPrim = -1;
         const float a = dot(wray.d, wray.d);
+        if (__builtin_amdgcn_ballot_w64(!recip_domain(2.f * a)) == 0) sweep_closest(wray, a, recip_of(2.f * a), bestT, bestSlot, bestPrim);
+        else sweep_closest(wray, a, 2.f * a, bestT, bestSlot, bestPrim);
+        PSTAT(13);
+        return tree.finish_hit(wray, bestT, bestT, bestSlot, bestPrim, best);
+    }
+    // twoA: 2 a as a float or as its Recip (hit_sphere_q), wave-uniformly
+    template <class D>
+    HRT_D void sweep_closest(const Ray& wray, float a, D twoA, float& bestT, int& bestSlot, int& bestPrim) const
+    {
         for (int l = 0; l < nLeaves; l++)
         {
             const NodeQ n = leaf(l);
@@ -675,12 +684,10 @@ struct TracerFlat {
                 if (!hit_box(wray, f.a, f.b, 0.001f, 1e30f)) continue;
                 PSTAT(8);
                 float t;
-                if (hit_sphere_ta(wray, a, xyz(f.c), f.c.w, t) && t > 0.001f && t < 1e30f && t < 1e29f && t < bestT)
+                if (hit_sphere_q(wray, a, twoA, xyz(f.c), f.c.w, t) && t > 0.001f && t < 1e30f && t < 1e29f && t < bestT)
                 { bestT = t; bestSlot = i; bestPrim = wbits(f.b); }
             }
         }
-        PSTAT(13);
-        return tree.finish_hit(wray, bestT, bestT, bestSlot, bestPrim, best);
     }
 
     template <bool COUNT>
@@ -690,8 +697,14 @@ struct TracerFlat {
         // An any-hit query is an OR over the instances whose sphere test the walk reaches, and by the lemma above the walk reaches
         // an instance iff the instance's OWN box test passes (tMax is fixed here, and a box that contains the instance's can only
         // turn a miss into a hit): the leaf boxes decide nothing, so they are not tested, and the order is free.
-        bool hit = false;
         const float a = dot(wray.d, wray.d);
+        if (__builtin_amdgcn_ballot_w64(!recip_domain(2.f * a)) == 0) return sweep_occluded(wray, a, recip_of(2.f * a), tMaxWorld);
+        return sweep_occluded(wray, a, 2.f * a, tMaxWorld);
+    }
+    template <class D>
+    HRT_D bool sweep_occluded(const Ray& wray, float a, D twoA, float tMaxWorld) const
+    {
+        bool hit = false;
         for (int l = 0; l < nLeaves; l++)
         {
             const NodeQ n = leaf(l);
@@ -703,7 +716,7 @@ struct TracerFlat {
                 if (hit || !hit_box(wray, f.a, f.b, 0.001f, tMaxWorld)) continue;
                 PSTAT(12);
                 float t;
-                if (hit_sphere_ta(wray, a, xyz(f.c), f.c.w, t) && t > 0.001f && t < tMaxWorld) hit = true;
+                if (hit_sphere_q(wray, a, twoA, xyz(f.c), f.c.w, t) && t > 0.001f && t < tMaxWorld) hit = true;
             }
             if (__builtin_amdgcn_ballot_w64(!hit) == 0) break;      // every live lane is occluded
         }

@@ -18,7 +18,8 @@ int  hrt_math_probe(hrt_ctx* ctx, int fn, int n, const float* x, const float* y,
 
 /* test hook: compares a trimmed device-side function with its IEEE definition for EVERY float of its stated domain, on the
  * device (which: 0 = 1/sqrt(x) of Normalize for x in [1e-20, +inf], 1 = the square root of the hemisphere sampler for +0 and
- * [2^-96, +inf]).  *mismatches = number of differing results (0 expected), *first_bad (may be NULL) = bits of the smallest one. */
+ * [2^-96, +inf], 2 = the reciprocal of inv_dir over its domain, 3 and 4 = the divide by a per-ray reciprocal over every numerator for
+ * 1028 denominators and over 2^34 hashed pairs; hrt_runtime.hip states each domain).  *mismatches = number of differing results (0 expected), *first_bad (may be NULL) = bits of the smallest one. */
 int  hrt_math_exhaustive(hrt_ctx* ctx, int which, uint64_t* mismatches, uint32_t* first_bad);
 
 /* test hooks, host code only (no device, no context): what hrt_scene_upload computes on the host for the SECOND tree of a scene of
