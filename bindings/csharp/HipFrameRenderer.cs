@@ -33,6 +33,22 @@ namespace ILGPU_Raytracing.Engine
         {
             fixed (HrtFrameParams* fp = &frame)
                 HipRaytrace.Check(_ctx, HipRaytrace.hrt_render_frame(_ctx, fp, null, null, null));      // blocking, results stay on the device
+            return Present(outW, outH, taau);
+        }
+
+        /// <summary>One step of a progressive frame: samples [sampleBegin, frame.spp) of the frame, then the same presentation as
+        /// Render.  sampleBegin 0 starts the frame; a later step passes the same frame with a larger spp and sampleBegin = the spp of
+        /// the step before.  The returned preview is what Render(frame) would return at frame.spp samples, and the last step's is the
+        /// finished frame.  Throws InvalidOperationException when the step does not continue the last one.</summary>
+        public ReadOnlySpan<int> RenderProgressive(in HrtFrameParams frame, int sampleBegin, int outW, int outH, bool taau)
+        {
+            fixed (HrtFrameParams* fp = &frame)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_render_progressive(_ctx, fp, null, sampleBegin, null, null));   // blocking, results stay on the device
+            return Present(outW, outH, taau);
+        }
+
+        private ReadOnlySpan<int> Present(int outW, int outH, bool taau)
+        {
             if (_display.Length != outW * outH) _display = new int[outW * outH];
             var pp = new HrtPresentParams { out_width = outW, out_height = outH, mode = taau ? 1 : 0 };   // tunables <= 0: the reference's 0.075 / 0.10 / 1.25
             fixed (int* dst = _display)

@@ -110,6 +110,9 @@ namespace ILGPU_Raytracing.Engine
         [DllImport(Lib)] public static extern int hrt_scene_download_array(IntPtr ctx, int dev, int array, void* dst, long cap, long* count);
         [DllImport(Lib)] public static extern int hrt_scene_download_tlas(IntPtr ctx, int dev, TLASNode* nodes, long capNodes, int* indices, long capIndices, InstanceRecord* instances, long capInstances, long* counts);
         [DllImport(Lib)] public static extern int hrt_render_frame(IntPtr ctx, HrtFrameParams* p, HrtRenderOpts* opts, HrtOutputs* outputs, HrtStats* stats);
+        // progressive frames: samples [sampleBegin, p->spp) of the frame p describes; afterwards every output equals hrt_render_frame(p).
+        // sampleBegin 0 starts a frame, > 0 continues the last one (same params except spp, sampleBegin = its spp; hrt_present may run between)
+        [DllImport(Lib)] public static extern int hrt_render_progressive(IntPtr ctx, HrtFrameParams* p, HrtRenderOpts* opts, int sampleBegin, HrtOutputs* outputs, HrtStats* stats);
         [DllImport(Lib)] public static extern int hrt_present(IntPtr ctx, HrtPresentParams* p, int* outColorHost);
         [DllImport(Lib)] public static extern int hrt_synchronize(IntPtr ctx, HrtStats* stats);
         [DllImport(Lib)] public static extern int hrt_reset_history(IntPtr ctx);

@@ -951,19 +951,30 @@ struct SplitK {
     int sBegin, sEnd, group, nGroups;
     int local, nLocal;       // this lane's slot in the scratch planes and their length: lanes of the launch's tiles, not image pixels
 };
+// PROG (hrt_render_progressive): the call renders samples [pk->sBegin, k.spp) of a frame whose samples [0, pk->sBegin) an earlier
+// call rendered.  Lframe (the raw in-order sum, before the 1/spp scale) starts from the carried plane and is stored back to it, so
+// the sum runs through the same additions in the same order as in one call.  Progressive sample groups need no PROG here: their
+// kernel only places the groups over [sBegin, k.spp), and split_resolve_pixel<true> continues the carried sum.
+struct ProgK {
+    hrt_float3* carry;       // raw Lframe per global pixel index: read when sBegin > 0, always written
+    int sBegin;              // first sample of this call
+};
 // REUSE = false: a frame with both ReSTIR reuse switches off (the launch knows); the import code and the arguments only it reads
 // (previous reservoirs, previous camera) are compiled out instead of being carried -- and spilled -- through the bounce loop.
-template <class TR, bool COUNT, bool SPLIT = false, bool REUSE = true>
+template <class TR, bool COUNT, bool SPLIT = false, bool REUSE = true, bool PROG = false>
 HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, const DFramebuffer& fb,
-                            const DReservoir& resPrev, const DReservoir& resCur, int64_t nPix, int index, Cnt<COUNT>& C, const SplitK* sk = nullptr)
+                            const DReservoir& resPrev, const DReservoir& resCur, int64_t nPix, int index, Cnt<COUNT>& C, const SplitK* sk = nullptr,
+                            const ProgK* pk = nullptr)
 {
     if (index == 0 && fb.cameraId && (!SPLIT || sk->group == 0)) fb.cameraId[0] = k.debugCamSeq;
 
     int px = index % hrt_imax(1, k.width), py = index / hrt_imax(1, k.width);
     const int sppAll = hrt_imax(1, k.spp);
-    const int sFirst = SPLIT ? sk->sBegin : 0;
+    int sFirst = SPLIT ? sk->sBegin : 0;
+    if constexpr (PROG && !SPLIT) sFirst = pk->sBegin;
     const int spp = SPLIT ? sk->sEnd : sppAll;           // end of this lane's sample range
     F3 Lframe = mk3(0.f, 0.f, 0.f);
+    if constexpr (PROG && !SPLIT) { if (pk->sBegin > 0) Lframe = ld3(&pk->carry[index]); }
     auto add_sample = [&](int sIdx, F3 c) {              // Lframe += SafeColor(Li), RTRay.cs:320 -- or hand the term to the resolve
         if (SPLIT) sk->li[(size_t)sIdx * (size_t)sk->nLocal + (size_t)sk->local] = to3(c);
         else Lframe = Lframe + c;
@@ -1171,19 +1182,26 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
 
     F3 Lout = Lframe * (1.0f / (float)sppAll);
     int io = index; asm volatile("" : "+v"(io));          // addresses of the stores derived here, not carried through the loop
+    if constexpr (PROG) pk->carry[io] = to3(Lframe);
     if (fb.radiance) fb.radiance[io] = to3(Lout);
     fb.color[io] = pack_rgba8(Lout);
     fb.depth[io] = cam_distance(k, ld3(&gb.worldPos[io]));
     fb.objectId[io] = gb.objId[io];
 }
 
-// second half of a SPLIT frame: ordered sample sum (:320-324), reservoir of the last sample that reached a diffuse vertex
+// second half of a SPLIT frame: ordered sample sum (:320-324), reservoir of the last sample that reached a diffuse vertex.
+// PROG: the sum continues the carried one over this call's samples [sBegin, spp) and is stored back; without a reservoir in any
+// group resCur keeps what the earlier calls left.
+template <bool PROG = false>
 HRT_D void split_resolve_pixel(const FrameK& k, const DGBuffer& gb, const DFramebuffer& fb, const DReservoir& resCur, int index,
-                               const hrt_float3* li, const float* stage, int nGroups, int local, int nLocal)
+                               const hrt_float3* li, const float* stage, int nGroups, int local, int nLocal,
+                               hrt_float3* carry = nullptr, int sBegin = 0)
 {
     const int spp = hrt_imax(1, k.spp);
     F3 Lframe = mk3(0.f, 0.f, 0.f);
-    for (int s = 0; s < spp; s++) Lframe = Lframe + ld3(&li[(size_t)s * (size_t)nLocal + (size_t)local]);
+    if constexpr (PROG) { if (sBegin > 0) Lframe = ld3(&carry[index]); }
+    for (int s = PROG ? sBegin : 0; s < spp; s++) Lframe = Lframe + ld3(&li[(size_t)s * (size_t)nLocal + (size_t)local]);
+    if constexpr (PROG) carry[index] = to3(Lframe);
     const size_t P = (size_t)nLocal;
     for (int g = nGroups - 1; g >= 0; g--)
     {

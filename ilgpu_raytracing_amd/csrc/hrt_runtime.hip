@@ -337,6 +337,56 @@ hrt_wf_resolve_kernel(FrameK k, WfGeom g, DGBuffer gb, DFramebuffer fb, DReservo
 }
 
 // ---------------------------------------------------------------------------------------
+// Progressive frames (hrt_render_progressive): the same pixel code with PROG set -- samples [sBegin, k.spp) of the frame, the
+// raw sample sum carried in a per-pixel plane between calls.  Separate entry points, so the kernels of hrt_render_frame keep
+// their code; production tracers only (no COUNT variants: counting frames cannot be progressive).
+// ---------------------------------------------------------------------------------------
+template <class TR, bool REUSE = true>
+__global__ void __launch_bounds__(256, PtWaves<TR>::value)
+hrt_path_trace_prog_kernel(TR tr, FrameK k, DGBuffer gb, DFramebuffer fb, DReservoir resPrev, DReservoir resCur,
+                           long long nPix, TileMap tm, hrt_float3* carry, int sBegin)
+{
+    Cnt<false> C;
+    ProgK pk; pk.carry = carry; pk.sBegin = sBegin;
+    int x, y;
+    if (tile_pixel(tm, k, x, y, blockIdx.x)) path_trace_pixel<TR, false, false, REUSE, true>(tr, k, gb, fb, resPrev, resCur, nPix, y * k.width + x, C, nullptr, &pk);
+}
+
+// groups of perGroup samples over [sBegin, k.spp): the split kernel's pixel code with the groups moved (the scratch planes are
+// indexed by absolute sample, as in a one-shot frame of k.spp samples)
+template <class TR, bool REUSE = true>
+__global__ void __launch_bounds__(256, PtWaves<TR>::value)
+hrt_path_trace_split_prog_kernel(TR tr, FrameK k, DGBuffer gb, DFramebuffer fb, DReservoir resPrev, DReservoir resCur,
+                                 long long nPix, TileMap tm, hrt_float3* li, float* stage, int nGroups, int perGroup, int sBegin)
+{
+    Cnt<false> C;
+    const int g = blockIdx.x / tm.nTiles;
+    SplitK sk;
+    sk.li = li; sk.stage = stage; sk.group = g; sk.nGroups = nGroups;
+    sk.sBegin = sBegin + g * perGroup; sk.sEnd = min(sk.sBegin + perGroup, k.spp);
+    const int tileBlock = blockIdx.x - g * tm.nTiles;
+    sk.local = tileBlock * (int)blockDim.x + (int)threadIdx.x; sk.nLocal = tm.nTiles * (int)blockDim.x;
+    int x, y;
+    if (tile_pixel(tm, k, x, y, tileBlock)) path_trace_pixel<TR, false, true, REUSE>(tr, k, gb, fb, resPrev, resCur, nPix, y * k.width + x, C, &sk);
+}
+
+__global__ void __launch_bounds__(256)
+hrt_split_resolve_prog_kernel(FrameK k, DGBuffer gb, DFramebuffer fb, DReservoir resCur, long long nPix, TileMap tm, const hrt_float3* li, const float* stage,
+                              int nGroups, hrt_float3* carry, int sBegin)
+{
+    int x, y;
+    if (tile_pixel(tm, k, x, y, blockIdx.x)) split_resolve_pixel<true>(k, gb, fb, resCur, y * k.width + x, li, stage, nGroups,
+                                                                       (int)(blockIdx.x * blockDim.x + threadIdx.x), tm.nTiles * (int)blockDim.x, carry, sBegin);
+}
+
+__global__ void __launch_bounds__(256)
+hrt_wf_resolve_prog_kernel(FrameK k, WfGeom g, DGBuffer gb, DFramebuffer fb, DReservoir resCur, WfBuffers W, hrt_float3* carry)
+{
+    int ord = blockIdx.x * 256 + threadIdx.x;
+    if (ord < g.nOrd) wf_resolve_pixel<true>(k, g, gb, fb, resCur, W, ord, carry);
+}
+
+// ---------------------------------------------------------------------------------------
 // Presentation kernels (hrt_post.hpp)
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -532,6 +582,8 @@ struct DeviceState {
     DGBuffer gb{};
     DFramebuffer fb{};
     DReservoir resA{}, resB{};
+    hrt_float3* prog_carry = nullptr;          // hrt_render_progressive: raw sample sum (Lframe before 1/spp) per global pixel index, 12 B/px;
+                                               // allocated by the first progressive call, at the size of the per-pixel buffers
     unsigned long long* counters = nullptr;   // 2 x 10
     int row_begin = 0, row_end = 0;            // rows [row_begin,row_end) ...
     int strip_n = 1, strip_i = 0;              // ... of which this device owns 8-row strips s with s % strip_n == strip_i
@@ -569,6 +621,14 @@ struct hrt_ctx {
     int width = 0, height = 0;
     long long max_resident_paths = 0;          // hrt_set_workspace_limit: 0 = kWfMaxPaths
     std::vector<std::pair<char*, size_t>> pinned;   // hrt_host_register: page-locked ranges of the caller (gather targets)
+    // the progressive frame a continuation (hrt_render_progressive with sample_begin > 0) may extend: what its last call rendered.
+    // Cleared by every call that changes what the next samples would see (frames, scene changes, history reset).
+    struct {
+        bool valid = false;
+        hrt_frame_params p{};                  // params of the last call; p.spp = samples rendered so far
+        int rb = 0, re = 0, sn = 1, si = 0;    // row range and strips, normalised as the render call normalises them
+        uint32_t pathFlags = 0;                // HRT_FLAG_REFERENCE_LAYOUT | MEGAKERNEL | STREAMED | TREELETS of the calls
+    } prog;
 };
 
 namespace {
@@ -611,6 +671,8 @@ void free_pixels(DeviceState& d)
                     d.resA.L, d.resA.wi, d.resA.pdf, d.resA.w, d.resA.wSum, d.resA.m, d.resA.lightId,
                     d.resB.L, d.resB.wi, d.resB.pdf, d.resB.w, d.resB.wSum, d.resB.m, d.resB.lightId};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (d.prog_carry) (void)hipFree(d.prog_carry);
+    d.prog_carry = nullptr;
     d.gb = DGBuffer{}; d.fb = DFramebuffer{}; d.resA = DReservoir{}; d.resB = DReservoir{};
     d.nPix = 0;
 }
@@ -1284,18 +1346,24 @@ template <class TR> struct PackedFeat { static constexpr int value = -1; };
 template <int F> struct PackedFeat<TracerPackedT<F>> { static constexpr int value = F; };
 
 template <class TR>
+// carry != nullptr: a progressive call (hrt_render_progressive) renders samples [sBegin, k.spp) and carries the raw sample sum in
+// carry (per global pixel index) -- the organisation is chosen as for a frame of the k.spp - sBegin samples this call renders
 int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, const TileMap& tm, int width,
-                   const DReservoir& resPrev, const DReservoir& resCur, long long nPix, bool count, bool mega, bool treelets = false)
+                   const DReservoir& resPrev, const DReservoir& resCur, long long nPix, bool count, bool mega, bool treelets = false,
+                   hrt_float3* carry = nullptr, int sBegin = 0)
 {
     unsigned long long* cnt1 = d.counters + 10;
     if (tm.nTiles <= 0) return HRT_OK;
+    const bool prog = carry != nullptr;
+    if (!prog) sBegin = 0;
     if (mega || k.maxDepth > 64)
     {
         const dim3 grid(tm.nTiles), block(64 * tm.wpb);
         // frames without ReSTIR reuse: the leaf-sweep tracer's kernels with the import code compiled out (hrt_device.hpp, REUSE)
         const bool noReuse = std::is_same<TR, TracerFlat>::value && !count && k.enableTemporal == 0 && k.enableSpatial == 0;
         // sample groups when the tile gives the machine less than ~5 rounds of waves
-        const int sppN = k.spp > 1 ? k.spp : 1;
+        const int sppAll = k.spp > 1 ? k.spp : 1;
+        const int sppN = sppAll - sBegin;                            // samples of this call
         const long long waves = (long long)tm.nTiles * tm.wpb, slots = (long long)d.n_cu * 4 * HRT_PT_WAVES;
         int nGroups = 1;
         if (!count && k.maxDepth <= 64 && sppN > 1 && waves > 0 && waves < 5 * slots)
@@ -1306,7 +1374,7 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
             nGroups = (sppN + perGroup - 1) / perGroup;
             // scratch planes over the lanes of THIS launch's tiles (a rank's share of the frame), not over the image
             const size_t nLocal = (size_t)tm.nTiles * 64 * (size_t)tm.wpb;
-            const size_t need = ((size_t)sppN * 3 + (size_t)nGroups * 12) * nLocal;
+            const size_t need = ((size_t)sppAll * 3 + (size_t)nGroups * 12) * nLocal;
             if (need > d.split_floats)
             {
                 if (d.split_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.split_mem); d.split_mem = nullptr; d.split_floats = 0; }
@@ -1315,10 +1383,25 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
                 d.split_mem = (float*)v; d.split_floats = need;
             }
             hrt_float3* li = (hrt_float3*)d.split_mem;
-            float* stage = d.split_mem + (size_t)sppN * 3 * nLocal;
+            float* stage = d.split_mem + (size_t)sppAll * 3 * nLocal;
+            if (prog)
+            {
+                if (noReuse) { if constexpr (std::is_same<TR, TracerFlat>::value) hipLaunchKernelGGL((hrt_path_trace_split_prog_kernel<TR, false>), dim3(tm.nTiles * nGroups), block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, li, stage, nGroups, perGroup, sBegin); }
+                else hipLaunchKernelGGL((hrt_path_trace_split_prog_kernel<TR>), dim3(tm.nTiles * nGroups), block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, li, stage, nGroups, perGroup, sBegin);
+                hipLaunchKernelGGL(hrt_split_resolve_prog_kernel, grid, block, 0, d.stream, k, d.gb, d.fb, resCur, nPix, tm, (const hrt_float3*)li, (const float*)stage, nGroups, carry, sBegin);
+                HIPCHK(c, hipGetLastError());
+                return HRT_OK;
+            }
             if (noReuse) { if constexpr (std::is_same<TR, TracerFlat>::value) hipLaunchKernelGGL((hrt_path_trace_split_kernel<TR, false>), dim3(tm.nTiles * nGroups), block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, li, stage, nGroups, perGroup); }
             else hipLaunchKernelGGL((hrt_path_trace_split_kernel<TR>), dim3(tm.nTiles * nGroups), block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, li, stage, nGroups, perGroup);
             hipLaunchKernelGGL(hrt_split_resolve_kernel, grid, block, 0, d.stream, k, d.gb, d.fb, resCur, nPix, tm, (const hrt_float3*)li, (const float*)stage, nGroups);
+            HIPCHK(c, hipGetLastError());
+            return HRT_OK;
+        }
+        if (prog)
+        {
+            if (noReuse) { if constexpr (std::is_same<TR, TracerFlat>::value) hipLaunchKernelGGL((hrt_path_trace_prog_kernel<TR, false>), grid, block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, carry, sBegin); }
+            else hipLaunchKernelGGL((hrt_path_trace_prog_kernel<TR>), grid, block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, carry, sBegin);
             HIPCHK(c, hipGetLastError());
             return HRT_OK;
         }
@@ -1332,11 +1415,12 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     g.tilesX8 = (width + 7) / 8;
     g.nOrd = g.tilesX8 * d.n_strips * 64;
     const int spp = k.spp > 1 ? k.spp : 1;
+    const int nS = spp - sBegin;                 // samples of this call: [sBegin, spp)
     long long maxPaths = kWfMaxPaths;
     if (c->max_resident_paths > 0) maxPaths = c->max_resident_paths;              // hrt_set_workspace_limit
     long long sb = maxPaths / g.nOrd;
     if (sb < 1) sb = 1;
-    if (sb > spp) sb = spp;
+    if (sb > nS) sb = nS;
     // Two sample batches in flight: the walks of one are latency-bound and leave the vector units idle most of the time, the
     // shade / finish / resolve kernels of the other fill them (measured first as two processes sharing the card: configs 4 / 5
     // -11 % / -7 %).  A frame that fits one batch is cut into two halves; only the ordered steps -- the per-pixel sample sum
@@ -1344,11 +1428,11 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     // ... a frame that fits one batch is cut in two only while each half still fills the machine (measured: halves of 16.6 M paths
     // config 3 -5.5 %, config 4 +-0; halves of 8.3 M paths config 5 +13 %)
     constexpr long long kMinHalfBatchPaths = 12000000;
-    const bool severalBatches = sb < spp;
-    const bool halves = !severalBatches && spp >= 2 && (long long)((spp + 1) / 2) * g.nOrd >= kMinHalfBatchPaths;
-    const int nBatchesNatural = (int)((spp + sb - 1) / sb);
+    const bool severalBatches = sb < nS;
+    const bool halves = !severalBatches && nS >= 2 && (long long)((nS + 1) / 2) * g.nOrd >= kMinHalfBatchPaths;
+    const int nBatchesNatural = (int)((nS + sb - 1) / sb);
     const int nLanes = severalBatches ? std::min(kBatchLanes, nBatchesNatural) : (halves ? std::min(kBatchLanes, 2) : 1);
-    if (nLanes >= 2 && !severalBatches && sb > (spp + 1) / 2) sb = (spp + 1) / 2;
+    if (nLanes >= 2 && !severalBatches && sb > (nS + 1) / 2) sb = (nS + 1) / 2;
     const long long batchPaths = sb * (long long)g.nOrd;
     const int nRanges = (int)((batchPaths + kRange - 1) / kRange);
     const long long cap = (long long)nRanges * kRange;
@@ -1372,7 +1456,7 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     constexpr bool fuse = PackedFeat<TR>::value == 0;
     for (int j = 0; j < nLanes; j++) Wl[j].pingpong = fuse ? 1 : 0;
     int batch = 0;
-    for (int b0 = 0; b0 < spp; b0 += (int)sb, batch++)
+    for (int b0 = sBegin; b0 < spp; b0 += (int)sb, batch++)
     {
         const int lane = batch % nLanes;
         const WfBuffers& W = Wl[lane];
@@ -1512,7 +1596,8 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
         }
         // ordered part: Lframe is summed in sample order and resCur keeps its last writer, so a batch resolves after its predecessor
         if (batch > 0 && nLanes >= 2) HIPCHK(c, hipStreamWaitEvent(sMain, d.evLane[(batch - 1) % nLanes][2], 0));
-        hipLaunchKernelGGL(hrt_wf_resolve_kernel, gridP, block, 0, sMain, k, g, d.gb, d.fb, resCur, W);
+        if (prog) hipLaunchKernelGGL(hrt_wf_resolve_prog_kernel, gridP, block, 0, sMain, k, g, d.gb, d.fb, resCur, W, carry);
+        else      hipLaunchKernelGGL(hrt_wf_resolve_kernel, gridP, block, 0, sMain, k, g, d.gb, d.fb, resCur, W);
         HIPCHK(c, hipGetLastError());
         if (nLanes >= 2) HIPCHK(c, hipEventRecord(d.evLane[lane][2], sMain));
     }
@@ -1834,6 +1919,7 @@ catch (...) { return on_exception(c, "hrt_synchronize"); }
 int hrt_scene_upload(hrt_ctx* c, const hrt_scene_desc* s)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
+    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     if (!s) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: scene is NULL");
     const void* src[15] = {s->tlasNodes, s->tlasInstanceIndices, s->instances, s->blasNodes, s->spherePrimIdx, s->spheres,
                            s->triPrimIdx, s->meshPositions, s->meshTris, s->meshTexcoords, s->meshTriUVs, s->triMatIndex,
@@ -2507,6 +2593,7 @@ int apply_update(hrt_ctx* c, int policy, const char* who, const std::function<in
 int hrt_scene_update_instances(hrt_ctx* c, const int32_t* ids, int32_t n, const hrt_affine3x4* xf, int32_t policy, hrt_bvh_update_stats* st)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
+    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_instances: no scene uploaded");
     if (n < 0 || (n > 0 && (!ids || !xf))) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_instances: n instances need ids and transforms");
     {
@@ -2534,6 +2621,7 @@ catch (...) { return on_exception(c, "hrt_scene_update_instances"); }
 int hrt_scene_update_positions(hrt_ctx* c, int64_t first, int64_t n, const hrt_float3* positions, int32_t policy, hrt_bvh_update_stats* st)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
+    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_positions: no scene uploaded");
     if (first < 0 || n < 0 || first + n > c->n_positions || (n > 0 && !positions))
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_positions: vertex range outside meshPositions");
@@ -2594,6 +2682,7 @@ catch (...) { return on_exception(c, "hrt_scene_update_positions"); }
 int hrt_scene_update_spheres(hrt_ctx* c, int64_t first, int64_t n, const hrt_sphere* spheres, int32_t policy, hrt_bvh_update_stats* st)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
+    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_spheres: no scene uploaded");
     if (first < 0 || n < 0 || first + n > c->n_spheres || (n > 0 && !spheres))
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_spheres: range outside spheres");
@@ -2651,6 +2740,7 @@ catch (...) { return on_exception(c, "hrt_scene_download_tlas"); }
 int hrt_reset_history(hrt_ctx* c)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
+    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     int rc = hrt_synchronize(c, nullptr);
     if (rc != HRT_OK) return rc;
     for (DeviceState& d : c->dev)
@@ -2672,32 +2762,69 @@ try {
 }
 catch (...) { return on_exception(c, "hrt_reset_history"); }
 
-int hrt_render_frame(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_opts* opts, const hrt_outputs* out, hrt_stats* stats)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    if (!p) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: params is NULL");
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_render_frame: no scene uploaded (call hrt_scene_upload first)");
-    if (p->width <= 0 || p->height <= 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: width/height must be positive");
-    if ((int64_t)p->width * p->height > 0x7FFFFFFFLL) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: image too large for int pixel indices");
-    if (p->maxDepth < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: maxDepth must be >= 0");
+// hrt_render_frame (progBegin < 0) and hrt_render_progressive (progBegin = sample_begin >= 0): one body, the progressive call renders
+// samples [progBegin, spp) and carries the raw sample sum in DeviceState::prog_carry; a continuation (progBegin > 0) keeps the G-buffer
+// of the call that started the frame instead of running primary visibility again.
+static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_opts* opts, const hrt_outputs* out, hrt_stats* stats,
+                       const char* who, int progBegin)
+{
+    const bool prog = progBegin >= 0, cont = progBegin > 0;
+    if (!prog) c->prog.valid = false;          // a one-shot frame ends any progressive one
+    if (!p) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": params is NULL");
+    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": no scene uploaded (call hrt_scene_upload first)");
+    if (p->width <= 0 || p->height <= 0) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": width/height must be positive");
+    if ((int64_t)p->width * p->height > 0x7FFFFFFFLL) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": image too large for int pixel indices");
+    if (p->maxDepth < 0) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": maxDepth must be >= 0");
     const uint32_t flags = opts ? opts->flags : 0u;
     int rb = opts ? opts->row_begin : 0, re = opts ? opts->row_end : 0;
     int sn = opts && opts->strip_n > 0 ? opts->strip_n : 1, si = opts ? opts->strip_i : 0;
     if (rb == 0 && re == 0) re = p->height;
-    if (rb < 0 || re > p->height || rb > re) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: row range outside the image");
-    if (si < 0 || si >= sn) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: strip_i must be in [0, strip_n)");
+    if (rb < 0 || re > p->height || rb > re) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": row range outside the image");
+    if (si < 0 || si >= sn) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": strip_i must be in [0, strip_n)");
     const bool nosync = (flags & HRT_FLAG_NO_SYNC) != 0;
-    if (nosync && out) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: HRT_FLAG_NO_SYNC frames cannot gather to host (outputs must be NULL)");
+    if (nosync && out) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": HRT_FLAG_NO_SYNC frames cannot gather to host (outputs must be NULL)");
     const bool reuse = (p->enableTemporalReuse != 0 || p->enableSpatialReuse != 0);
     const int nd = (int)c->dev.size();
     const bool primaryOnly = (flags & HRT_FLAG_PRIMARY_ONLY) != 0;
-    if (primaryOnly && (flags & HRT_FLAG_SKIP_PRIMARY)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: PRIMARY_ONLY and SKIP_PRIMARY exclude each other");
+    if (primaryOnly && (flags & HRT_FLAG_SKIP_PRIMARY)) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": PRIMARY_ONLY and SKIP_PRIMARY exclude each other");
     if (reuse && !primaryOnly && !(flags & HRT_FLAG_EXCHANGED) && (sn > 1 || rb != 0 || re != p->height))
-        return fail(c, HRT_ERR_INVALID_STATE, "hrt_render_frame: ReSTIR reuse needs every pixel's G-buffer and previous reservoir: render reuse frames as full images, "
+        return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": ReSTIR reuse needs every pixel's G-buffer and previous reservoir: render reuse frames as full images, "
                     "or exchange tiles between processes and say so (HRT_FLAG_PRIMARY_ONLY / HRT_FLAG_EXCHANGED; one ctx over several devices exchanges tiles itself)");
-    if (reuse && nd > 1 && nosync) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_frame: multi-device reuse frames cannot be enqueued with HRT_FLAG_NO_SYNC");
+    if (reuse && nd > 1 && nosync) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": multi-device reuse frames cannot be enqueued with HRT_FLAG_NO_SYNC");
     const int64_t nPix = (int64_t)p->width * p->height;
     const bool count = (flags & HRT_FLAG_COUNTERS) != 0;
+    constexpr uint32_t kPathFlags = HRT_FLAG_REFERENCE_LAYOUT | HRT_FLAG_MEGAKERNEL | HRT_FLAG_STREAMED | HRT_FLAG_TREELETS;
+    if (prog)
+    {   // every refusal comes before anything is enqueued or allocated: a refused call leaves the frame it would continue intact
+        if (flags & (HRT_FLAG_COUNTERS | HRT_FLAG_PRIMARY_ONLY | HRT_FLAG_SKIP_PRIMARY | HRT_FLAG_EXCHANGED))
+            return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": HRT_FLAG_COUNTERS, PRIMARY_ONLY, SKIP_PRIMARY and EXCHANGED cannot be used with progressive frames");
+        if (p->spp < 1) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": params->spp must be >= 1");
+        if (p->spp <= progBegin) return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": params->spp (" + std::to_string(p->spp) + ") must exceed sample_begin (" + std::to_string(progBegin) + ")");
+        if (cont)
+        {
+            const auto& q = c->prog;
+            if (!q.valid)
+                return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": no progressive frame to continue (start one with sample_begin = 0; hrt_render_frame, scene uploads / updates, "
+                            "hrt_reset_history and resizes end it)");
+            if (progBegin != q.p.spp)
+                return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": sample_begin (" + std::to_string(progBegin) + ") differs from the samples rendered so far (" + std::to_string(q.p.spp) + ")");
+#define HRT_PROG_FIELD(f) { #f, offsetof(hrt_frame_params, f), sizeof(p->f) }
+            static const struct { const char* name; size_t off, size; } kFields[] = {
+                HRT_PROG_FIELD(width), HRT_PROG_FIELD(height), HRT_PROG_FIELD(frame), HRT_PROG_FIELD(cam), HRT_PROG_FIELD(prevCam),
+                HRT_PROG_FIELD(dirLightDir), HRT_PROG_FIELD(dirLightRadiance), HRT_PROG_FIELD(skyTintTop), HRT_PROG_FIELD(skyTintBottom),
+                HRT_PROG_FIELD(debugCamSeq), HRT_PROG_FIELD(enableTemporalReuse), HRT_PROG_FIELD(enableSpatialReuse), HRT_PROG_FIELD(rngLockNoise),
+                HRT_PROG_FIELD(maxDepth)};
+#undef HRT_PROG_FIELD
+            for (const auto& f : kFields)        // bitwise: every field but spp
+                if (std::memcmp((const char*)p + f.off, (const char*)&q.p + f.off, f.size) != 0)
+                    return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": params->" + f.name + " differs from the progressive frame being continued");
+            if (rb != q.rb || re != q.re) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": the row range differs from the progressive frame being continued");
+            if (sn != q.sn || si != q.si) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": strip_n / strip_i differ from the progressive frame being continued");
+            if ((flags & kPathFlags) != q.pathFlags)
+                return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": the path-selecting flags (REFERENCE_LAYOUT, MEGAKERNEL, STREAMED, TREELETS) differ from the progressive frame being continued");
+        }
+        c->prog.valid = false;                 // until this call is enqueued
+    }
 
     if (nPix != c->dev[0].nPix || c->dev[0].ring_head >= DeviceState::kRing)
     {   // resize (or a full event ring) drains the frames in flight first
@@ -2708,6 +2835,13 @@ try {
     {
         int rc = ensure_pixels(c, d, nPix);
         if (rc != HRT_OK) return rc;
+        if (prog && !d.prog_carry)
+        {   // not initialised: the call that starts a frame (sample_begin 0) seeds its sums with zero and only stores
+            void* v = nullptr;
+            HIPCHK(c, hipSetDevice(d.device_id));
+            HIPCHK(c, hipMalloc(&v, (size_t)nPix * sizeof(hrt_float3)));
+            d.prog_carry = (hrt_float3*)v;
+        }
     }
     c->width = p->width; c->height = p->height;
 
@@ -2801,7 +2935,7 @@ try {
         }
         hipEvent_t* ev = d.ev[d.ring_head];
         HIPCHK(c, hipEventRecord(ev[0], d.stream));
-        if (tm.nTiles > 0 && !(flags & HRT_FLAG_SKIP_PRIMARY))
+        if (tm.nTiles > 0 && !(flags & HRT_FLAG_SKIP_PRIMARY) && !cont)
         {
             const dim3 grid(tm.nTiles), block(64 * tm.wpb);
             int rcs = with_tracer(d, [&](auto tr) -> int {
@@ -2825,7 +2959,7 @@ try {
         }
         HIPCHK(c, hipEventRecord(ev[1], d.stream));
     }
-    if (exchange)
+    if (exchange && !cont)
     {   // SpatialCompatible reads objId / normalWS / worldPos of the CURRENT frame at other pixels (RTRay.cs:363-374)
         int rc = exchange_arrays(1, [&](DeviceState& src, DeviceState& dst) -> int {
             int r;
@@ -2846,7 +2980,8 @@ try {
         DReservoir resCur = even ? d.resA : d.resB;
         hipEvent_t* ev = d.ev[d.ring_head];
         int rcs = primaryOnly ? HRT_OK : with_tracer(d, [&](auto tr) -> int {
-            return run_path_stage(c, d, tr, k, tm, p->width, resPrev, resCur, (long long)nPix, count, mega, (flags & HRT_FLAG_TREELETS) != 0);
+            return run_path_stage(c, d, tr, k, tm, p->width, resPrev, resCur, (long long)nPix, count, mega, (flags & HRT_FLAG_TREELETS) != 0,
+                                  prog ? d.prog_carry : nullptr, prog ? progBegin : 0);
         });
         if (rcs != HRT_OK) return rcs;
         HIPCHK(c, hipEventRecord(ev[2], d.stream));
@@ -2902,15 +3037,34 @@ try {
                 catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
             });
         for (std::thread& t : workers) t.join();
-        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_render_frame: gather of device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
+        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], std::string(who) + ": gather of device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
     }
     else
         for (DeviceState& d : c->dev) { int rc = gather_device(d, c); if (rc != HRT_OK) return rc; }
     for (DeviceState& d : c->dev) d.ring_head++;
+    if (prog)
+    {
+        c->prog.valid = true; c->prog.p = *p;
+        c->prog.rb = rb; c->prog.re = re; c->prog.sn = sn; c->prog.si = si; c->prog.pathFlags = flags & kPathFlags;
+    }
     if (nosync) { if (stats) std::memset(stats, 0, sizeof(*stats)); return HRT_OK; }
     return hrt_synchronize(c, stats);
 }
+
+int hrt_render_frame(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_opts* opts, const hrt_outputs* out, hrt_stats* stats)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    return render_impl(c, p, opts, out, stats, "hrt_render_frame", -1);
+}
 catch (...) { return on_exception(c, "hrt_render_frame"); }
+
+int hrt_render_progressive(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_opts* opts, int32_t sample_begin, const hrt_outputs* out, hrt_stats* stats)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (sample_begin < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_render_progressive: sample_begin must be >= 0");
+    return render_impl(c, p, opts, out, stats, "hrt_render_progressive", sample_begin);
+}
+catch (...) { return on_exception(c, "hrt_render_progressive"); }
 
 int hrt_present(hrt_ctx* c, const hrt_present_params* pp, int32_t* out_color_host)
 try {

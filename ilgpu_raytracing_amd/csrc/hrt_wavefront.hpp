@@ -743,14 +743,17 @@ HRT_D void wf_finish_shade_wave(const TracerPackedT<FEAT>& tr, const FrameK& k, 
 }
 
 // ------------------------------------------------------------------ resolve: ordered sample sum, reservoir hand-off, framebuffer store (:320-324)
+// PROG (hrt_render_progressive): Lframe is carried in `carry` (raw sum per global pixel index) instead of W.accum, so it runs on
+// from the call that rendered the samples before g.batchStart; every batch stores it back, the last one as well.
+template <bool PROG = false>
 HRT_D void wf_resolve_pixel(const FrameK& k, const WfGeom& g, const DGBuffer& gb, const DFramebuffer& fb, const DReservoir& resCur,
-                            const WfBuffers& W, int ord)
+                            const WfBuffers& W, int ord, hrt_float3* carry = nullptr)
 {
     int x, y;
     if (!ord_pixel(g, k, ord, x, y)) return;
     const int index = y * k.width + x;
     if (index == 0 && fb.cameraId && g.batchStart == 0) fb.cameraId[0] = k.debugCamSeq;
-    F3 Lframe = g.batchStart == 0 ? mk3(0.f, 0.f, 0.f) : W.accum.ld3(0, ord);
+    F3 Lframe = g.batchStart == 0 ? mk3(0.f, 0.f, 0.f) : (PROG ? ld3(&carry[index]) : W.accum.ld3(0, ord));
     const int hitMask = gb.hitMask[index];
     if (hitMask == 0)
     {
@@ -779,7 +782,8 @@ HRT_D void wf_resolve_pixel(const FrameK& k, const WfGeom& g, const DGBuffer& gb
             resCur.m[index] = W.stage.ldi(G_M, pid);
         }
     }
-    if (!g.lastBatch) { W.accum.st3(0, ord, Lframe); return; }
+    if constexpr (PROG) { carry[index] = to3(Lframe); if (!g.lastBatch) return; }
+    else if (!g.lastBatch) { W.accum.st3(0, ord, Lframe); return; }
     F3 Lout = Lframe * (1.0f / (float)hrt_imax(1, k.spp));
     if (fb.radiance) fb.radiance[index] = to3(Lout);
     fb.color[index] = pack_rgba8(Lout);

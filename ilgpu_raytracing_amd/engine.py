@@ -55,6 +55,8 @@ def _load(path, hooks=False):
     L.hrt_scene_download_tlas.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                           C.POINTER(C.c_int64)]
     L.hrt_render_frame.argtypes = [C.c_void_p, C.POINTER(T.FrameParams), C.POINTER(T.RenderOpts), C.POINTER(T.Outputs), C.POINTER(T.Stats)]
+    L.hrt_render_progressive.argtypes = [C.c_void_p, C.POINTER(T.FrameParams), C.POINTER(T.RenderOpts), C.c_int32, C.POINTER(T.Outputs),
+                                         C.POINTER(T.Stats)]
     L.hrt_synchronize.argtypes = [C.c_void_p, C.POINTER(T.Stats)]
     L.hrt_present.argtypes = [C.c_void_p, C.POINTER(T.PresentParams), C.c_void_p]
     L.hrt_device_buffers.argtypes = [C.c_void_p, C.c_int, C.POINTER(T.DeviceViews)]
@@ -546,6 +548,38 @@ class RTRenderer(FrameHost):
         self.last_params = params
         return st
 
+    def render_progressive(self, params, sample_begin, outputs=None, flags=0, rows=None, strips=None):
+        """Samples [sample_begin, params.spp) of the frame `params` describes (hrt_render_progressive): afterwards every output is
+        bit for bit the frame render_params(params) gives.  sample_begin = 0 starts a progressive frame; sample_begin > 0 continues
+        the last one, with params equal to its params except spp, sample_begin = its spp, and the same rows, strips and
+        REFERENCE_LAYOUT / MEGAKERNEL / STREAMED / TREELETS flags.  FLAG_NO_SYNC only enqueues (outputs must be None).  Returns Stats."""
+        sample_begin = _progressive_args(params.spp, sample_begin, flags, outputs)
+        st = T.Stats()
+        opts = T.RenderOpts(flags, rows[0] if rows else 0, rows[1] if rows else 0,
+                            strips[0] if strips else 1, strips[1] if strips else 0)
+        self._check(self._L.hrt_render_progressive(self._ctx, C.byref(params), C.byref(opts), sample_begin,
+                                                   C.byref(outputs) if outputs is not None else None, C.byref(st)))
+        self.last_params = params
+        return st
+
+    def refine(self, params, schedule, outputs=None, flags=0):
+        """Renders the frame `params` describes progressively, one call per entry of `schedule`: cumulative sample counts such as
+        (8, 32, 256).  Returns a generator that yields (spp_so_far, Stats) after each call, when the outputs (and present()) show the frame at
+        spp_so_far samples; stop iterating to stop early.  params.spp is ignored; `params` is not modified.
+        The schedule and flags are checked here, before the first call."""
+        steps = _refine_schedule(schedule)
+        _progressive_args(steps[0], 0, flags, outputs)
+        p = T.FrameParams.from_buffer_copy(params)
+
+        def run():
+            begin = 0
+            for spp in steps:
+                p.spp = spp
+                st = self.render_progressive(p, begin, outputs, flags)
+                begin = spp
+                yield spp, st
+        return run()
+
     def render_frame(self, width, height, frame, dt=0.0, outputs=None, flags=0, rows=None):
         """RenderDirectToPbo(pbo, width, height, frame, dt) without the presentation step, with width x height as the internal size
         (a render scale of 1); render_direct applies the render scale."""
@@ -715,6 +749,41 @@ class RTRenderer(FrameHost):
 
 # ------------------------------------------------------------------ SceneManager / BvhManager (Engine/SceneManager.cs, BvhManager.cs)
 _QUERIES = {"closest": T.QUERY_CLOSEST, "occluded": T.QUERY_OCCLUDED}
+
+
+_PROGRESSIVE_FORBIDDEN = {T.FLAG_COUNTERS: "FLAG_COUNTERS", T.FLAG_PRIMARY_ONLY: "FLAG_PRIMARY_ONLY",
+                          T.FLAG_SKIP_PRIMARY: "FLAG_SKIP_PRIMARY", T.FLAG_EXCHANGED: "FLAG_EXCHANGED"}
+
+
+def _progressive_args(spp, sample_begin, flags, outputs):
+    """The argument rules of hrt_render_progressive, checked before the library is called.  Returns sample_begin as an int."""
+    if isinstance(sample_begin, bool) or not isinstance(sample_begin, (int, np.integer)):
+        raise TypeError("sample_begin must be an int, got %s" % type(sample_begin).__name__)
+    sample_begin = int(sample_begin)
+    if sample_begin < 0:
+        raise ValueError("sample_begin must be >= 0, got %d" % sample_begin)
+    if spp < 1:
+        raise ValueError("params.spp must be >= 1, got %d" % spp)
+    if spp <= sample_begin:
+        raise ValueError("params.spp (%d) must exceed sample_begin (%d)" % (spp, sample_begin))
+    for bit, name in _PROGRESSIVE_FORBIDDEN.items():
+        if flags & bit:
+            raise ValueError("%s cannot be used with progressive frames" % name)
+    if (flags & T.FLAG_NO_SYNC) and outputs is not None:
+        raise ValueError("FLAG_NO_SYNC calls cannot gather to host: outputs must be None")
+    return sample_begin
+
+
+def _refine_schedule(schedule):
+    steps = [int(s) for s in schedule]
+    if not steps:
+        raise ValueError("schedule must name at least one cumulative sample count")
+    if steps[0] < 1:
+        raise ValueError("schedule must start at >= 1 samples, got %d" % steps[0])
+    for a, b in zip(steps, steps[1:]):
+        if b <= a:
+            raise ValueError("schedule must be strictly increasing cumulative sample counts, got %d after %d" % (b, a))
+    return steps
 
 
 def _rays_arg(a, name):

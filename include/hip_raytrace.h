@@ -258,6 +258,28 @@ int  hrt_render_frame(hrt_ctx* ctx, const hrt_frame_params* params,
                       const hrt_outputs* outputs,       /* may be NULL: leave results on device */
                       hrt_stats* stats);                /* may be NULL */
 
+/* ---- progressive frames: one frame refined over several calls, bit-exact.
+ * Renders samples [sample_begin, params->spp) of the frame `params` describes.  On return every output
+ * (host `outputs`, hrt_device_views, resCur) holds exactly what hrt_render_frame(params) would: the frame at
+ * params->spp samples.
+ *   - sample_begin == 0 starts a progressive frame: primary visibility, then samples [0, spp).  params->spp >= 1.
+ *   - sample_begin > 0 continues the progressive frame last rendered on this ctx, without primary visibility.  It needs
+ *     params bitwise identical to the previous call's except spp, sample_begin == the previous call's spp, and the same
+ *     row range, strips and path-selecting flags (REFERENCE_LAYOUT, MEGAKERNEL, STREAMED, TREELETS); otherwise, or after
+ *     an hrt_render_frame, hrt_scene_upload, hrt_scene_update_*, hrt_reset_history or resize in between, it returns
+ *     HRT_ERR_INVALID_STATE with a message naming what differs.  params->spp <= sample_begin: HRT_ERR_INVALID_ARG.
+ *   - hrt_present (the preview), hrt_trace_rays, hrt_device_buffers, hrt_frame_times and hrt_synchronize may run in between.
+ *   - flags: REFERENCE_LAYOUT, MEGAKERNEL, STREAMED, TREELETS and NO_SYNC (outputs must then be NULL, as for frames; several
+ *     continuations may be enqueued back to back).  COUNTERS, PRIMARY_ONLY, SKIP_PRIMARY and EXCHANGED: HRT_ERR_INVALID_ARG
+ *     (the one-process-per-GPU reuse protocol is not progressive).
+ *   - ReSTIR reuse: legal wherever a reuse frame is (a full image; one ctx over several device slots), exact in the same sense.
+ *   - a refused call changes no device state: a following valid continuation is unaffected.
+ * Exact because the sample sum is one in-order f32 sum carried between calls unscaled, the random stream of a sample depends
+ * only on (pixel, frame, lock, sample index), and resCur keeps its last writer.  The carried sum is a per-device plane of
+ * 12 B per pixel (99.5 MB at 3840x2160), allocated by the first progressive call and freed by hrt_destroy (or a resize). */
+int  hrt_render_progressive(hrt_ctx* ctx, const hrt_frame_params* params, const hrt_render_opts* opts,
+                            int32_t sample_begin, const hrt_outputs* outputs, hrt_stats* stats);
+
 /* Waits for every frame enqueued with HRT_FLAG_NO_SYNC.  stats (may be NULL): kernel_ms[]
  * = per-launch HIP-event time summed over those frames (max over devices), frames = their
  * number.  A blocking hrt_render_frame is enqueue + hrt_synchronize. */
