@@ -959,6 +959,11 @@ struct ProgK {
     hrt_float3* carry;       // raw Lframe per global pixel index: read when sBegin > 0, always written
     int sBegin;              // first sample of this call
 };
+// Sample starts of path_trace_pixel keep the pixel's sample-independent values in LDS (17 KB per 256-thread workgroup) for the
+// tracers that set this (TracerFlat: its kernels stay at 5 waves per SIMD without scratch); the tree walkers' kernels, whose
+// LDS and registers already bound their occupancy, derive them again at every sample start.
+template <class TR> struct StagePixel { static constexpr bool value = false; };
+
 // REUSE = false: a frame with both ReSTIR reuse switches off (the launch knows); the import code and the arguments only it reads
 // (previous reservoirs, previous camera) are compiled out instead of being carried -- and spilled -- through the bounce loop.
 template <class TR, bool COUNT, bool SPLIT = false, bool REUSE = true, bool PROG = false>
@@ -994,22 +999,50 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
         // behind an optimisation barrier, so that one register lives across the bounce loop instead of the ~17 the compiler would
         // otherwise keep -- and, at 96 registers, spill to scratch memory (68 B per lane of HBM traffic).
         auto fresh_index = [&]() { int i = index; asm volatile("" : "+v"(i)); return i; };
-        // The G-buffer vertex every sample starts from (:221-230) is re-read from memory at each sample start (an L2
-        // hit) instead of being held in 14 registers across the whole bounce loop.
+        // The G-buffer vertex every sample starts from (:221-230) is re-read at each sample start (from memory, an L2 hit, or
+        // from LDS, below) instead of being held in 14 registers across the whole bounce loop.
         F3 pos, nrm, alb, I; int shade; float ior;
         Rng rng;
-        auto start_sample = [&](int sIdx) {
-            const int i = fresh_index();
-            const int w = hrt_imax(1, k.width);
-            const SeedBase sb = seed_base((uint32_t)(i % w), (uint32_t)(i / w), k.frame, 0xC0FFEEu, k.rngLockNoise);
+        // Everything but the sample's own seed is the same at every sample start.  With StagePixel<TR> the first start derives it
+        // and parks it in the lane's LDS column (17 dwords, [field][thread] like s_res below), and later starts read it back and
+        // run rng_for_sample only; otherwise every start derives it again.
+        constexpr bool kStage = StagePixel<TR>::value;
+        __shared__ float s_px[kStage ? 17 : 1][256];
+        auto start_sample = [&](int sIdx, bool first) {
+            const int t = threadIdx.x;
+            SeedBase sb;
+            if (kStage && !first)
+            {
+                sb.s0 = __float_as_uint(s_px[0][t]); sb.lane1b = __float_as_uint(s_px[1][t]); sb.rot_px = __float_as_uint(s_px[2][t]);
+                pos = mk3(s_px[3][t], s_px[4][t], s_px[5][t]);
+                nrm = mk3(s_px[6][t], s_px[7][t], s_px[8][t]);
+                alb = mk3(s_px[9][t], s_px[10][t], s_px[11][t]);
+                shade = __float_as_int(s_px[12][t]); ior = s_px[13][t];
+                I = mk3(s_px[14][t], s_px[15][t], s_px[16][t]);
+            }
+            else
+            {
+                const int i = fresh_index();
+                const int w = hrt_imax(1, k.width);
+                sb = seed_base((uint32_t)(i % w), (uint32_t)(i / w), k.frame, 0xC0FFEEu, k.rngLockNoise);
+                pos = ld3(&gb.worldPos[i]);
+                nrm = normalize(ld3(&gb.normalWS[i]));
+                alb = ld3(&gb.baseColor[i]);
+                const int packedMat = gb.matId[i];
+                shade = packedMat & 0xFFFF;
+                ior = (float)((packedMat >> 16) & 0xFFFF) / 1000.f;
+                I = normalize(pos - cv3(k.cam.origin));
+                if constexpr (kStage)
+                {
+                    s_px[0][t] = __uint_as_float(sb.s0); s_px[1][t] = __uint_as_float(sb.lane1b); s_px[2][t] = __uint_as_float(sb.rot_px);
+                    s_px[3][t] = pos.x; s_px[4][t] = pos.y; s_px[5][t] = pos.z;
+                    s_px[6][t] = nrm.x; s_px[7][t] = nrm.y; s_px[8][t] = nrm.z;
+                    s_px[9][t] = alb.x; s_px[10][t] = alb.y; s_px[11][t] = alb.z;
+                    s_px[12][t] = __int_as_float(shade); s_px[13][t] = ior;
+                    s_px[14][t] = I.x; s_px[15][t] = I.y; s_px[16][t] = I.z;
+                }
+            }
             rng = rng_for_sample(sb, (uint32_t)sIdx);
-            pos = ld3(&gb.worldPos[i]);
-            nrm = normalize(ld3(&gb.normalWS[i]));
-            alb = ld3(&gb.baseColor[i]);
-            const int packedMat = gb.matId[i];
-            shade = packedMat & 0xFFFF;
-            ior = (float)((packedMat >> 16) & 0xFFFF) / 1000.f;
-            I = normalize(pos - cv3(k.cam.origin));
         };
         // resCur.Write (:42-47): every sample's first diffuse vertex writes the same slot and only the last write survives.
         // The latest one waits in the lane's own LDS column (8 dwords, [field][thread]: conflict-free; L is a function of the
@@ -1023,7 +1056,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
         // neighbours are still bouncing.  Per-pixel order is untouched (samples of a pixel stay sequential).
         int s = sFirst, depth = 0;
         bool wroteReservoir = false;            // per sample (RTRay.cs:231): every sample's first diffuse vertex writes resCur
-        start_sample(sFirst);
+        start_sample(sFirst, true);
         F3 Li = mk3(0.f, 0.f, 0.f), T = mk3(1.f, 1.f, 1.f);
         if (k.maxDepth <= 0) { for (; s < spp; s++) add_sample(s, safe_color(Li)); }
 
@@ -1032,13 +1065,15 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
             PSTAT(0);
             bool ended = false;
             {
-                Ray ray;
+                // every branch hands (offset normal, direction) to the one ray_with_normal_offset after them: a wave whose lanes
+                // take several branches builds the bounce ray once instead of once per branch (glass: twice)
+                F3 rayN, rayD;
                 bool terminated = false;
                 if (shade == HRT_SHADING_MIRROR)
                 {   // :235-244
                     PSTAT(1);
                     F3 dirR = I - nrm * (2.f * dot(I, nrm));
-                    ray = ray_with_normal_offset(pos, nrm, dirR);
+                    rayN = nrm; rayD = dirR;
                     T = T * alb;
                 }
                 else if (shade == HRT_SHADING_GLASS)
@@ -1067,7 +1102,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                     float Fr = r0 + (1.f - r0) * (om2 * om2 * om);
                     float xi = rng.next_f();
                     bool reflect = (!refrOk || xi < Fr);
-                    ray = reflect ? ray_with_normal_offset(pos, Nuse, dirR) : ray_with_normal_offset(pos, -Nuse, dirT);
+                    rayN = reflect ? Nuse : -Nuse; rayD = reflect ? dirR : dirT;
                     if (refrOk && xi >= Fr)
                     {
                         F3 tint = (alb.x == 0.f && alb.y == 0.f && alb.z == 0.f) ? mk3(1.f, 1.f, 1.f) : alb;
@@ -1112,7 +1147,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                         wroteReservoir = true;
                     }
                     F3 wi = sample_hemisphere_cosine(fr, rng);
-                    ray = ray_with_normal_offset(pos, nrm, wi);
+                    rayN = nrm; rayD = wi;
                     T = T * alb;
                     if (depth >= 3)
                     {   // :306-312
@@ -1122,6 +1157,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                         else T = T * (1.0f / maxC);
                     }
                 }
+                const Ray ray = ray_with_normal_offset(pos, rayN, rayD);
                 if (terminated) ended = true;
                 else
                 {   // TraceNext :659-671 -- the one closest-hit site of the bounce loop
@@ -1147,7 +1183,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                 if (s < spp)
                 {   // next sample starts again from the G-buffer vertex (:212-231)
                     wroteReservoir = false;
-                    start_sample(s);
+                    start_sample(s, false);
                     Li = mk3(0.f, 0.f, 0.f); T = mk3(1.f, 1.f, 1.f);
                     depth = 0;
                 }

@@ -40,15 +40,21 @@ using namespace hrt;
 // camera through a compact square and walk nearly the same BVH nodes.  Workgroup ids are
 // dealt round-robin over the 8 XCDs by the dispatcher; remap() hands every XCD one
 // contiguous band of tiles so each private 4 MiB L2 caches one region of the BVH instead
-// of all of it (bijective form of the T1 remap, cdna_hip_programming.md).
+// of all of it (bijective form of the T1 remap, cdna_hip_programming.md).  Frames of a small scene (<= kSmallSceneNodes in
+// the fused kernels) skip the remap (band = 0): their BVH is a few cache lines, and the identity map gives every XCD tiles from
+// the whole image (60 tiles per row is not a multiple of 8), so no XCD waits on the heaviest band of rows.
 // ---------------------------------------------------------------------------------------
-struct TileMap { int tilesX, tilesY, nTiles, wpb; };      // wpb: waves (8x8 pixel tiles) per workgroup, side by side
+struct TileMap { int tilesX, tilesY, nTiles, wpb, band; };      // wpb: waves (8x8 pixel tiles) per workgroup, side by side
 
 __device__ __forceinline__ bool tile_pixel(const TileMap& tm, const FrameK& k, int& x, int& y, int orig)
 {
-    int q = tm.nTiles >> 3, r = tm.nTiles & 7;
-    int xcd = orig & 7, seq = orig >> 3;
-    int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
+    int tile = orig;
+    if (tm.band)
+    {
+        int q = tm.nTiles >> 3, r = tm.nTiles & 7;
+        int xcd = orig & 7, seq = orig >> 3;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
+    }
     int ty = tile / tm.tilesX, tx = tile - ty * tm.tilesX;
     int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     x = (tx * tm.wpb + wave) * 8 + (lane & 7);
@@ -2879,6 +2885,7 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
     };
     // pixel kernels: four waves per workgroup, each on an 8x8 tile, side by side (a 32x8 tile: the 256 lanes of the path-trace
     // kernels' launch bounds)
+    const bool mega = (flags & HRT_FLAG_MEGAKERNEL) ? true : ((flags & HRT_FLAG_STREAMED) ? false : c->small_scene);
     constexpr int ptWaves = 4;
     auto tile_map = [&](const DeviceState& d) {
         TileMap tm;
@@ -2886,12 +2893,12 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
         tm.tilesX = (p->width + 8 * ptWaves - 1) / (8 * ptWaves);
         tm.tilesY = d.n_strips;
         tm.nTiles = tm.tilesX * tm.tilesY;
+        tm.band = !(mega && c->small_scene);
         return tm;
     };
     // tracer variant: the smallest packed walker that covers the committed scene, or the reference layout
     const bool usePacked = c->packed_ok && !(flags & HRT_FLAG_REFERENCE_LAYOUT);
     const int variant = usePacked ? c->packed_feat : -1;
-    const bool mega = (flags & HRT_FLAG_MEGAKERNEL) ? true : ((flags & HRT_FLAG_STREAMED) ? false : c->small_scene);
     // production frames of a tiny fast-sphere scene in the fused kernel: wave-uniform sweep over the TLAS leaves
     const bool flat = variant == 0 && mega && !count && c->flat_leaves > 0;
     auto with_tracer = [&](DeviceState& d, auto fn) -> int {

@@ -723,5 +723,6 @@ struct TracerFlat {
         return hit;
     }
 };
+template <> struct StagePixel<TracerFlat> { static constexpr bool value = true; };
 
 } // namespace hrt
