@@ -69,6 +69,17 @@ namespace ILGPU_Raytracing.Engine
             return hit;
         }
 
+        /// <summary>Radiance along caller rays (hrt_trace_paths): ray i is path-traced as pixel key firstKey + i of the frame `p`
+        /// describes (reuse off), with its own origin and direction in place of the camera's.  Panoramas, probes, custom cameras.
+        /// The frame's own camera rays in pixel order give the frame's colour, radiance, depth and objectId bit for bit.</summary>
+        public void TracePaths(in HrtFrameParams p, ReadOnlySpan<HrtRay> rays, Span<HrtPathResult> results, long firstKey = 0, uint flags = 0)
+        {
+            if (results.Length < rays.Length) throw new ArgumentException("results is shorter than rays");
+            HrtFrameParams pp = p;
+            fixed (HrtRay* r = rays) fixed (HrtPathResult* o = results)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_trace_paths(_ctx, &pp, flags, r, rays.Length, firstKey, o, -1, null));
+        }
+
         /// <summary>Framebuffer.EnsureLength / RTTaa.Ensure side effect the host may want explicitly (camera cut).</summary>
         public void ResetHistory() => HipRaytrace.Check(_ctx, HipRaytrace.hrt_reset_history(_ctx));
 

@@ -93,6 +93,16 @@ namespace ILGPU_Raytracing.Engine
         public int instance, prim;                 // instance record; sphere or triangle index (miss: -1 / -1)
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtPathResult                  // hrt_path_result (32 bytes): PathTraceKernel (RTRay.cs:203-325) along a caller ray
+    {
+        public Float3 radiance;                    // Lout: mean over spp of SafeColor(Li), pre-pack
+        public int color;                          // PackRGBA8(radiance)
+        public float depth;                        // |worldPos - ray.origin|
+        public int objId;                          // primary hit, -1 on a miss
+        public int reserved0, reserved1;           // 0
+    }
+
     internal static unsafe class HipRaytrace
     {
         const string Lib = "hip_raytrace";        // libhip_raytrace.so
@@ -127,6 +137,7 @@ namespace ILGPU_Raytracing.Engine
         // (results: int[n] of 0/1).  dev < 0: host arrays, split over every device slot; dev >= 0: device pointers of that slot.  Blocking.
         public const int HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1;
         [DllImport(Lib)] public static extern int hrt_trace_rays(IntPtr ctx, int query, HrtRay* rays, long n, void* results, int dev, float* deviceMs);
+        [DllImport(Lib)] public static extern int hrt_trace_paths(IntPtr ctx, HrtFrameParams* p, uint flags, HrtRay* rays, long n, long firstKey, HrtPathResult* results, int dev, float* deviceMs);
 
         // native asset loader (optional: a C# host may keep MeshLoaderOBJ)
         [DllImport(Lib)] public static extern IntPtr hrth_scene_new();

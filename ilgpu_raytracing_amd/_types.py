@@ -174,10 +174,16 @@ class RayHit(C.Structure):            # hrt_ray_hit: TraceClosest's outputs + th
                 ("objId", C.c_int32), ("shade", C.c_int32), ("instance", C.c_int32), ("prim", C.c_int32)]
 
 
-assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 48
+class PathResult(C.Structure):        # hrt_path_result: one radiance query of hrt_trace_paths
+    _fields_ = [("radiance", Float3), ("color", C.c_int32), ("depth", C.c_float), ("objId", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PathResult) == 32
 
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1      # hrt_ray_query
-QUERY_CHUNK = 1 << 21                     # HRT_QUERY_CHUNK: rays per walk of one device slot
+QUERY_CHUNK = 1 << 21                     # HRT_QUERY_CHUNK: rays per walk of one device slot (and keys per radiance-query chunk)
+PATH_FLAGS = 4 | 16 | 32 | 256            # REFERENCE_LAYOUT | MEGAKERNEL | STREAMED | TREELETS: the flags hrt_trace_paths takes
 
 
 FLAG_COUNTERS = 1

@@ -963,15 +963,37 @@ struct ProgK {
 // tracers that set this (TracerFlat: its kernels stay at 5 waves per SIMD without scratch); the tree walkers' kernels, whose
 // LDS and registers already bound their occupancy, derive them again at every sample start.
 template <class TR> struct StagePixel { static constexpr bool value = false; };
+// RAYS (hrt_trace_paths, hrt_paths.hpp): the pixel's primary vertex came from a caller ray, not from the camera.  Key j (the pixel
+// index, which keys the RNG as in a frame) has its ray at rays[j - k0] and its result at out[j - k0]; its G-buffer slot is j - base in
+// the query's private planes.  The three camera-derived values -- view direction, miss direction, depth -- take the ray's own origin
+// and direction; the frame-only stores (resCur, cameraId) are left out.
+struct PathsK {
+    const hrt_ray* rays;
+    hrt_path_result* out;
+    int k0, k1;              // keys [k0, k1) of the launch
+    int base;                // G-buffer slot of key j: j - base
+    int x0, xw;              // columns [x0, x0 + xw) of the launch's rows
+};
+HRT_D F3 paths_origin(const PathsK* q, int j) { return ld3(&q->rays[j - q->k0].origin); }
+HRT_D F3 paths_dir(const PathsK* q, int j) { return ld3(&q->rays[j - q->k0].dir); }
+// the result record: two 16-byte stores (radiance, color | depth, objId, reserved = 0)
+HRT_D void paths_store(const PathsK* q, int j, F3 Lout, F3 worldPos, int objId)
+{
+    const F3 d = worldPos - paths_origin(q, j);
+    float4* o = reinterpret_cast<float4*>(&q->out[j - q->k0]);
+    o[0] = make_float4(Lout.x, Lout.y, Lout.z, __int_as_float(pack_rgba8(Lout)));
+    o[1] = make_float4(hrt_sqrt(d.x * d.x + d.y * d.y + d.z * d.z), __int_as_float(objId), 0.f, 0.f);   // DistanceFromCamera's expression
+}
 
 // REUSE = false: a frame with both ReSTIR reuse switches off (the launch knows); the import code and the arguments only it reads
 // (previous reservoirs, previous camera) are compiled out instead of being carried -- and spilled -- through the bounce loop.
-template <class TR, bool COUNT, bool SPLIT = false, bool REUSE = true, bool PROG = false>
+template <class TR, bool COUNT, bool SPLIT = false, bool REUSE = true, bool PROG = false, bool RAYS = false>
 HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, const DFramebuffer& fb,
                             const DReservoir& resPrev, const DReservoir& resCur, int64_t nPix, int index, Cnt<COUNT>& C, const SplitK* sk = nullptr,
-                            const ProgK* pk = nullptr)
+                            const ProgK* pk = nullptr, const PathsK* qk = nullptr)
 {
-    if (index == 0 && fb.cameraId && (!SPLIT || sk->group == 0)) fb.cameraId[0] = k.debugCamSeq;
+    static_assert(!(RAYS && (REUSE || PROG || COUNT)), "radiance queries run with reuse off, in one call, without counters");
+    if (!RAYS && index == 0 && fb.cameraId && (!SPLIT || sk->group == 0)) fb.cameraId[0] = k.debugCamSeq;
 
     int px = index % hrt_imax(1, k.width), py = index / hrt_imax(1, k.width);
     const int sppAll = hrt_imax(1, k.spp);
@@ -985,12 +1007,20 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
         else Lframe = Lframe + c;
     };
 
-    const int hitMask = gb.hitMask[index];
+    const int hitMask = gb.hitMask[RAYS ? index - qk->base : index];
 
     if (hitMask == 0)
     {
-        F3 c = safe_color(sky(k, primary_ray(k, px, py).d));
-        for (int s = sFirst; s < spp; s++) add_sample(s, c);     // :214-219, same value every sample
+        if constexpr (RAYS)
+        {
+            F3 c = safe_color(sky(k, paths_dir(qk, index)));
+            for (int s = sFirst; s < spp; s++) add_sample(s, c);
+        }
+        else
+        {
+            F3 c = safe_color(sky(k, primary_ray(k, px, py).d));
+            for (int s = sFirst; s < spp; s++) add_sample(s, c);     // :214-219, same value every sample
+        }
         if (SPLIT) sk->stage[((size_t)sk->group * 12 + 11) * (size_t)sk->nLocal + (size_t)sk->local] = 0.f;      // no reservoir from this group
     }
     else
@@ -1025,13 +1055,16 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                 const int i = fresh_index();
                 const int w = hrt_imax(1, k.width);
                 sb = seed_base((uint32_t)(i % w), (uint32_t)(i / w), k.frame, 0xC0FFEEu, k.rngLockNoise);
-                pos = ld3(&gb.worldPos[i]);
-                nrm = normalize(ld3(&gb.normalWS[i]));
-                alb = ld3(&gb.baseColor[i]);
-                const int packedMat = gb.matId[i];
+                int g = i;                                 // (no ternary on qk: the frame's lambda must not capture it)
+                if constexpr (RAYS) g = i - qk->base;
+                pos = ld3(&gb.worldPos[g]);
+                nrm = normalize(ld3(&gb.normalWS[g]));
+                alb = ld3(&gb.baseColor[g]);
+                const int packedMat = gb.matId[g];
                 shade = packedMat & 0xFFFF;
                 ior = (float)((packedMat >> 16) & 0xFFFF) / 1000.f;
-                I = normalize(pos - cv3(k.cam.origin));
+                if constexpr (RAYS) I = normalize(pos - paths_origin(qk, i));
+                else I = normalize(pos - cv3(k.cam.origin));
                 if constexpr (kStage)
                 {
                     s_px[0][t] = __uint_as_float(sb.s0); s_px[1][t] = __uint_as_float(sb.lane1b); s_px[2][t] = __uint_as_float(sb.rot_px);
@@ -1204,7 +1237,7 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
                 for (int f = 3; f < 8; f++) st[(f + 3) * P] = s_res[f][t];       // pdf, w, wSum, m, lightId
             }
         }
-        else if (haveRes)
+        else if (!RAYS && haveRes)
         {
             const int t = threadIdx.x;
             const int i = fresh_index();
@@ -1218,6 +1251,12 @@ HRT_D void path_trace_pixel(const TR& tr, const FrameK& k, const DGBuffer& gb, c
 
     F3 Lout = Lframe * (1.0f / (float)sppAll);
     int io = index; asm volatile("" : "+v"(io));          // addresses of the stores derived here, not carried through the loop
+    if constexpr (RAYS)
+    {
+        const int g = io - qk->base;
+        paths_store(qk, io, Lout, ld3(&gb.worldPos[g]), gb.objId[g]);
+        return;
+    }
     if constexpr (PROG) pk->carry[io] = to3(Lframe);
     if (fb.radiance) fb.radiance[io] = to3(Lout);
     fb.color[io] = pack_rgba8(Lout);

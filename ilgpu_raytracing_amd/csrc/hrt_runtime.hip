@@ -26,6 +26,7 @@
 #include "hrt_bvh.hpp"
 #include "hrt_post.hpp"
 #include "hrt_query.hpp"
+#include "hrt_paths.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
 #include "../../include/hrt_test_hooks.h"
@@ -34,33 +35,7 @@
 using namespace hrt;
 
 
-// ---------------------------------------------------------------------------------------
-// Pixel <-> lane mapping.  A 256-thread workgroup shades a 32x8 pixel tile: each of its 4
-// waves owns one 8x8 sub-tile (lane l -> (l&7, l>>3)), so the 64 rays of a wave leave the
-// camera through a compact square and walk nearly the same BVH nodes.  Workgroup ids are
-// dealt round-robin over the 8 XCDs by the dispatcher; remap() hands every XCD one
-// contiguous band of tiles so each private 4 MiB L2 caches one region of the BVH instead
-// of all of it (bijective form of the T1 remap, cdna_hip_programming.md).  Frames of a small scene (<= kSmallSceneNodes in
-// the fused kernels) skip the remap (band = 0): their BVH is a few cache lines, and the identity map gives every XCD tiles from
-// the whole image (60 tiles per row is not a multiple of 8), so no XCD waits on the heaviest band of rows.
-// ---------------------------------------------------------------------------------------
-struct TileMap { int tilesX, tilesY, nTiles, wpb, band; };      // wpb: waves (8x8 pixel tiles) per workgroup, side by side
-
-__device__ __forceinline__ bool tile_pixel(const TileMap& tm, const FrameK& k, int& x, int& y, int orig)
-{
-    int tile = orig;
-    if (tm.band)
-    {
-        int q = tm.nTiles >> 3, r = tm.nTiles & 7;
-        int xcd = orig & 7, seq = orig >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
-    }
-    int ty = tile / tm.tilesX, tx = tile - ty * tm.tilesX;
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    x = (tx * tm.wpb + wave) * 8 + (lane & 7);
-    y = k.row_begin + (ty * k.strip_n + k.strip_i) * 8 + (lane >> 3);   // 8-row strips dealt round-robin over tiles
-    return x < k.width && y < k.row_end;
-}
+#include "hrt_pixels.hpp"
 
 // TR = TracerPacked (fast, device-private layout) or TracerRef (the reference's array layout);
 // COUNT = work-counter build.
@@ -74,17 +49,6 @@ hrt_primary_kernel(TR tr, FrameK k, DGBuffer gb, TileMap tm, unsigned long long*
     C.flush(counters);
 }
 
-#ifndef HRT_PT_WAVES
-#define HRT_PT_WAVES 4   // 128-VGPR cap: 4 waves/SIMD hide the dependent node loads better than 2 at 204 VGPRs (measured)
-#endif
-// The leaf-sweep tracer is the exception: at 5 waves/SIMD (102 VGPRs, 112 bytes of scratch per lane) the fused kernel of
-// config 2 is 2 % faster than at 4 (VALU-bound: one more wave to issue from is worth the spill traffic); 6 and 3 lose 12 %.
-// Every other tracer spills two to four times as much there and keeps 4.
-template <class TR> struct PtWaves { static constexpr int value = HRT_PT_WAVES; };
-#ifndef HRT_PT_WAVES_FLAT
-#define HRT_PT_WAVES_FLAT (HRT_PT_WAVES + 1)
-#endif
-template <> struct PtWaves<TracerFlat> { static constexpr int value = HRT_PT_WAVES_FLAT; };
 template <class TR, bool COUNT, bool REUSE = true>
 __global__ void __launch_bounds__(256, PtWaves<TR>::value)
 hrt_path_trace_kernel(TR tr, FrameK k, DGBuffer gb, DFramebuffer fb, DReservoir resPrev, DReservoir resCur,
@@ -392,6 +356,7 @@ hrt_wf_resolve_prog_kernel(FrameK k, WfGeom g, DGBuffer gb, DFramebuffer fb, DRe
     if (ord < g.nOrd) wf_resolve_pixel<true>(k, g, gb, fb, resCur, W, ord, carry);
 }
 
+
 // ---------------------------------------------------------------------------------------
 // Presentation kernels (hrt_post.hpp)
 // ---------------------------------------------------------------------------------------
@@ -599,6 +564,9 @@ struct DeviceState {
     void* q_mem = nullptr; int64_t q_cap = 0;             // rays (32 B) + raw winners (16 B) + hits (48 B) per ray, then 8 hand-out counters
     void* q_host = nullptr; int64_t q_host_cap = 0;       // pinned staging of the host path: rays + hits per ray
     hipEvent_t q_ev[2] = {};
+    // radiance queries (hrt_trace_paths): rays and results are staged through q_mem / q_host; the chunk's G-buffer planes (48 B per slot)
+    // and the scratch planes of sample groups live here, never in the frame's buffers
+    void* p_mem = nullptr; size_t p_bytes = 0;
 };
 
 } // namespace
@@ -1634,6 +1602,8 @@ void free_query(DeviceState& d)
     if (d.q_host) (void)hipHostFree(d.q_host);
     for (hipEvent_t& e : d.q_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     d.q_mem = nullptr; d.q_host = nullptr; d.q_cap = d.q_host_cap = 0;
+    if (d.p_mem) (void)hipFree(d.p_mem);
+    d.p_mem = nullptr; d.p_bytes = 0;
 }
 
 // device staging for m rays (and the pinned host staging too when `host`); the caller has made d's device current
@@ -2768,6 +2738,26 @@ try {
 }
 catch (...) { return on_exception(c, "hrt_reset_history"); }
 
+// the kernels' frame constants of params (the row range and strips are the caller's)
+static FrameK frame_consts(const hrt_frame_params* p)
+{
+    FrameK k;
+    k.width = p->width; k.height = p->height; k.frame = p->frame;
+    k.row_begin = 0; k.row_end = p->height; k.strip_n = 1; k.strip_i = 0;
+    k.cam = p->cam; k.prevCam = p->prevCam;
+    k.dirLightDir = p->dirLightDir; k.dirLightRadiance = p->dirLightRadiance;
+    {   // Float3.Normalize(k.dirLightDir) (RTRay.cs:464) is the same for every vertex of the frame: evaluated here, by the contract's
+        // host definitions (IEEE sqrt and division, maxNum: include/hrt_math.h), instead of at every diffuse vertex on the device
+        const float x = p->dirLightDir.X, y = p->dirLightDir.Y, z = p->dirLightDir.Z;
+        const float inv = hrt_rsqrt(hrt_fmax(1e-20f, x * x + y * y + z * z));
+        k.dirLightN.X = x * inv; k.dirLightN.Y = y * inv; k.dirLightN.Z = z * inv;
+    }
+    k.skyTop = p->skyTintTop; k.skyBottom = p->skyTintBottom;
+    k.debugCamSeq = p->debugCamSeq; k.enableTemporal = p->enableTemporalReuse; k.enableSpatial = p->enableSpatialReuse;
+    k.rngLockNoise = p->rngLockNoise; k.spp = p->spp; k.maxDepth = p->maxDepth;
+    return k;
+}
+
 // hrt_render_frame (progBegin < 0) and hrt_render_progressive (progBegin = sample_begin >= 0): one body, the progressive call renders
 // samples [progBegin, spp) and carries the raw sample sum in DeviceState::prog_carry; a continuation (progBegin > 0) keeps the G-buffer
 // of the call that started the frame instead of running primary visibility again.
@@ -2867,20 +2857,8 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
     const bool even = (p->frame & 1) == 0;
     const bool exchange = reuse && nd > 1;      // ReSTIR reuse reads other tiles' G-buffer and previous reservoirs
     auto frame_k = [&](const DeviceState& d) {
-        FrameK k;
-        k.width = p->width; k.height = p->height; k.frame = p->frame;
+        FrameK k = frame_consts(p);
         k.row_begin = d.row_begin; k.row_end = d.row_end; k.strip_n = d.strip_n; k.strip_i = d.strip_i;
-        k.cam = p->cam; k.prevCam = p->prevCam;
-        k.dirLightDir = p->dirLightDir; k.dirLightRadiance = p->dirLightRadiance;
-        {   // Float3.Normalize(k.dirLightDir) (RTRay.cs:464) is the same for every vertex of the frame: evaluated here, by the contract's
-            // host definitions (IEEE sqrt and division, maxNum: include/hrt_math.h), instead of at every diffuse vertex on the device
-            const float x = p->dirLightDir.X, y = p->dirLightDir.Y, z = p->dirLightDir.Z;
-            const float inv = hrt_rsqrt(hrt_fmax(1e-20f, x * x + y * y + z * z));
-            k.dirLightN.X = x * inv; k.dirLightN.Y = y * inv; k.dirLightN.Z = z * inv;
-        }
-        k.skyTop = p->skyTintTop; k.skyBottom = p->skyTintBottom;
-        k.debugCamSeq = p->debugCamSeq; k.enableTemporal = p->enableTemporalReuse; k.enableSpatial = p->enableSpatialReuse;
-        k.rngLockNoise = p->rngLockNoise; k.spp = p->spp; k.maxDepth = p->maxDepth;
         return k;
     };
     // pixel kernels: four waves per workgroup, each on an 8x8 tile, side by side (a 32x8 tile: the 256 lanes of the path-trace
@@ -3256,6 +3234,174 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_trace_rays"); }
+
+// hrt_trace_paths: rays [begin, end) of one device slot, chunk by chunk on the slot's main stream (after any frame in flight): H2D of the
+// rays, primary kernel into the private G-buffer, fused path stage writing the result records, D2H.  A chunk is whole rows of width
+// keys (at most kQueryChunk slots), or a segment of at most kQueryChunk columns of one row when a row is wider.  *ms += kernel time.
+static int paths_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_frame_params& p, uint32_t flags, const hrt_ray* rays,
+                      hrt_path_result* results, int64_t begin, int64_t end, int64_t first_key, bool dev_ptrs, float* ms)
+{
+    HIPCHK(c, hipSetDevice(d.device_id));
+    auto registered = [&](const void* ptr, size_t bytes) {
+        for (const auto& r : cc.pinned) if ((const char*)ptr >= r.first && (const char*)ptr + bytes <= r.first + r.second) return true;
+        return false;
+    };
+    const hipStream_t st = d.stream;
+    const int64_t W = p.width, K1 = first_key + end;
+    // the frame's tracer for the scene (render_impl, with the fused path stage): TracerFlat for tiny sphere scenes, the smallest packed
+    // walker otherwise (its primary over the second tree where one describes the scene), TracerRef for REFERENCE_LAYOUT
+    const bool usePacked = cc.packed_ok && !(flags & HRT_FLAG_REFERENCE_LAYOUT);
+    const int variant = usePacked ? cc.packed_feat : -1;
+    PathsLaunch L;
+    L.variant = variant;
+    L.flat = variant == 0 && cc.flat_leaves > 0;
+    L.second = variant == 0 && !L.flat && d.any_ok;
+    L.S = d.dscene; L.P = d.dpacked; L.PAny = d.dpackedAny;
+    L.leaves = (const NodeQ*)d.packed[4]; L.nLeaves = cc.flat_leaves;
+    for (int64_t c0 = first_key + begin; c0 < K1; )
+    {
+        int64_t R = c0 / W, rows, x0, xw;
+        if (W <= kQueryChunk) { x0 = 0; xw = W; rows = std::min<int64_t>(kQueryChunk / W, (K1 + W - 1) / W - R); }
+        else { x0 = (c0 - R * W) / kQueryChunk * kQueryChunk; xw = std::min<int64_t>(kQueryChunk, W - x0); rows = 1; }
+        const int64_t c1 = std::min<int64_t>(K1, (R + rows - 1) * W + x0 + xw);
+        const int64_t m = c1 - c0, slots = rows * xw;
+        FrameK k = frame_consts(&p);
+        k.row_begin = (int)R; k.row_end = (int)(R + rows); k.height = k.row_end;
+        TileMap tm;
+        tm.wpb = 4;
+        tm.tilesX = (int)((xw + 31) / 32);
+        tm.tilesY = (int)((rows + 7) / 8);
+        tm.nTiles = tm.tilesX * tm.tilesY;
+        tm.band = !cc.small_scene;
+        // sample groups as run_path_stage forms them for a fused frame of this many tiles
+        const int sppAll = p.spp > 1 ? p.spp : 1;
+        const long long waves = (long long)tm.nTiles * tm.wpb, hwSlots = (long long)d.n_cu * 4 * HRT_PT_WAVES;
+        int nGroups = 1;
+        if (p.maxDepth <= 64 && sppAll > 1 && waves < 5 * hwSlots)
+            nGroups = (int)std::min<long long>(std::min(sppAll, 8), (16 * hwSlots + waves - 1) / waves);
+        int perGroup = sppAll;
+        if (nGroups > 1) { perGroup = (sppAll + nGroups - 1) / nGroups; nGroups = (sppAll + perGroup - 1) / perGroup; }
+        const size_t nLocal = (size_t)tm.nTiles * 256;
+        const size_t splitFloats = nGroups > 1 ? ((size_t)sppAll * 3 + (size_t)nGroups * 12) * nLocal : 0;
+        const size_t need = splitFloats * sizeof(float) + (size_t)slots * 48;
+        if (need > d.p_bytes)
+        {
+            if (d.p_mem) { HIPCHK(c, hipStreamSynchronize(st)); (void)hipFree(d.p_mem); d.p_mem = nullptr; d.p_bytes = 0; }
+            HIPCHK(c, hipMalloc(&d.p_mem, need));
+            d.p_bytes = need;
+        }
+        float* split = (float*)d.p_mem;
+        char* gbm = (char*)d.p_mem + splitFloats * sizeof(float);
+        DGBuffer gb;
+        gb.worldPos = (hrt_float3*)gbm; gb.normalWS = gb.worldPos + slots; gb.baseColor = gb.normalWS + slots;
+        gb.matId = (int32_t*)(gb.baseColor + slots); gb.objId = gb.matId + slots; gb.hitMask = gb.objId + slots;
+
+        if (dev_ptrs)
+        {   // the caller's device buffers hold rays and results: no staging, only the timing events
+            if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
+        }
+        else
+        {
+            int rc = ensure_query(c, d, m, true);
+            if (rc != HRT_OK) return rc;
+        }
+        char* qbase = (char*)d.q_mem;
+        const hrt_ray* src = rays + (c0 - first_key);
+        hrt_path_result* dst = results + (c0 - first_key);
+        const bool rayReg = !dev_ptrs && registered(src, (size_t)m * sizeof(hrt_ray));
+        const bool resReg = !dev_ptrs && registered(dst, (size_t)m * sizeof(hrt_path_result));
+        char* hostRays = (char*)d.q_host;
+        char* hostRes = (char*)d.q_host + (size_t)d.q_host_cap * 32;
+        PathsK q;
+        q.k0 = (int)c0; q.k1 = (int)c1; q.base = (int)(R * W + x0); q.x0 = (int)x0; q.xw = (int)xw;
+        if (dev_ptrs) { q.rays = src; q.out = dst; }
+        else
+        {
+            q.rays = (const hrt_ray*)qbase;
+            q.out = (hrt_path_result*)(qbase + (size_t)d.q_cap * 48);
+            if (!rayReg) std::memcpy(hostRays, src, (size_t)m * sizeof(hrt_ray));
+            HIPCHK(c, hipMemcpyAsync(qbase, rayReg ? (const void*)src : (const void*)hostRays, (size_t)m * sizeof(hrt_ray), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
+        L.k = k; L.tm = tm; L.q = q; L.gb = gb; L.split = split; L.nGroups = nGroups; L.perGroup = perGroup;
+        HIPCHK(c, paths_launch(L, st));
+        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
+        if (!dev_ptrs) HIPCHK(c, hipMemcpyAsync(resReg ? (void*)dst : (void*)hostRes, q.out, (size_t)m * sizeof(hrt_path_result), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        float t = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
+        *ms += t;
+        if (!dev_ptrs && !resReg) std::memcpy(dst, hostRes, (size_t)m * sizeof(hrt_path_result));
+        c0 = c1;
+    }
+    return HRT_OK;
+}
+
+int hrt_trace_paths(hrt_ctx* c, const hrt_frame_params* p, uint32_t flags, const hrt_ray* rays, int64_t n, int64_t first_key,
+                    hrt_path_result* results, int32_t dev, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (!p) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: params is NULL");
+    constexpr uint32_t kPathFlags = HRT_FLAG_REFERENCE_LAYOUT | HRT_FLAG_MEGAKERNEL | HRT_FLAG_STREAMED | HRT_FLAG_TREELETS;
+    if (flags & ~kPathFlags)
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: only the path-selecting flags (REFERENCE_LAYOUT, MEGAKERNEL, STREAMED, TREELETS) apply to radiance queries");
+    if (p->enableTemporalReuse != 0 || p->enableSpatialReuse != 0)
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: ReSTIR reuse needs a frame's reservoirs: set enableTemporalReuse and enableSpatialReuse to 0");
+    if (p->width <= 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: params->width must be positive");
+    if (p->maxDepth < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: maxDepth must be >= 0");
+    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: n must be >= 0");
+    if (first_key < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: first_key must be >= 0");
+    if (first_key > 0x7FFFFFFFLL - n) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: first_key + n exceeds 2^31 - 1 (keys are int pixel indices)");
+    if (n > 0 && (!rays || !results)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: rays and results are needed when n > 0");
+    const int nd = (int)c->dev.size();
+    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: device slot out of range");
+    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_paths: no scene uploaded (call hrt_scene_upload first)");
+    if (n == 0) return HRT_OK;
+    if (dev >= 0)
+    {
+        DeviceState& d = c->dev[(size_t)dev];
+        HIPCHK(c, hipSetDevice(d.device_id));
+        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, results, (size_t)n * sizeof(hrt_path_result)))
+            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: with dev >= 0, rays and results must be device memory of that slot's device, large enough for n");
+        if (((uintptr_t)rays | (uintptr_t)results) & 15) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: device rays and results must be 16-byte aligned");
+        float ms = 0.f;
+        int rc = paths_slot(c, *c, d, *p, flags, rays, results, 0, n, first_key, true, &ms);
+        if (rc != HRT_OK) return rc;
+        if (device_ms) *device_ms = ms;
+        return HRT_OK;
+    }
+    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as hrt_trace_rays)
+    if (in_device_memory(rays) || in_device_memory(results))
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: with dev < 0, rays and results must be host memory (pass the slot of device pointers as dev)");
+    std::vector<float> ms((size_t)nd, 0.f);
+    auto part = [&](int i) { return n * i / nd; };
+    if (nd > 1)
+    {
+        std::vector<int> rcs((size_t)nd, HRT_OK);
+        std::vector<std::string> errs((size_t)nd);
+        std::vector<std::thread> workers;
+        for (int i = 0; i < nd; i++)
+            workers.emplace_back([&, i]() {
+                try
+                {
+                    rcs[(size_t)i] = paths_slot(nullptr, *c, c->dev[(size_t)i], *p, flags, rays, results, part(i), part(i + 1), first_key, false, &ms[(size_t)i]);
+                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
+                }
+                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
+            });
+        for (std::thread& t : workers) t.join();
+        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_paths: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
+    }
+    else
+    {
+        int rc = paths_slot(c, *c, c->dev[0], *p, flags, rays, results, 0, n, first_key, false, &ms[0]);
+        if (rc != HRT_OK) return rc;
+    }
+    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_trace_paths"); }
 
 #ifdef HRT_TEST_HOOKS
 // test hook: evaluate hrt_math.h function `fn` on device 0 of ctx (see hrt_math_probe_kernel)

@@ -66,6 +66,8 @@ def _load(path, hooks=False):
     L.hrt_host_unregister.argtypes = [C.c_void_p, C.c_void_p]
     L.hrt_set_workspace_limit.argtypes = [C.c_void_p, C.c_int64]
     L.hrt_trace_rays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+    L.hrt_trace_paths.argtypes = [C.c_void_p, C.POINTER(T.FrameParams), C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                  C.c_int32, C.POINTER(C.c_float)]
     L.hrt_device_count.restype = C.c_int
     L.hrt_version.restype = C.c_char_p
     L.hrth_scene_new.restype = C.c_void_p
@@ -714,6 +716,98 @@ class RTRenderer(FrameHost):
         ints = out[:, 8:12].view(torch.int32)
         return dict(t=out[:, 0], normal=out[:, 1:4], albedo=out[:, 4:7], ior=out[:, 7],
                     objId=ints[:, 0], shade=ints[:, 1], instance=ints[:, 2], prim=ints[:, 3])
+
+    def trace_paths(self, origins, dirs, params, first_key=0, flags=0, slot=None):
+        """PathTraceKernel (RTRay.cs:203-325) along caller rays (hrt_trace_paths): ray i is shaded as pixel key j = first_key + i of
+        the frame `params` describes (RNG pixel (j % width, j // width)), with reuse off, its primary vertex TraceClosest(ray) and
+        the ray's own origin / direction where the frame uses the camera's (view direction, miss sky, depth).  origins, dirs: (n, 3)
+        float32, dirs used as given.  Camera rays (camera_rays(params)) give the frame's radiance, color, depth and objectId bit for bit.
+        numpy inputs: host path over every device slot; returns a structured array of T.PathResult.
+        torch tensors on a GPU: device path on the slot of their device; returns a dict of tensors radiance (n, 3) float32,
+        color, objId int32, depth float32."""
+        if not isinstance(params, T.FrameParams):
+            raise TypeError("params must be a FrameParams")
+        if params.enableTemporalReuse or params.enableSpatialReuse:
+            raise ValueError("trace_paths runs with ReSTIR reuse off: set enableTemporalReuse and enableSpatialReuse to 0")
+        if params.width <= 0 or params.maxDepth < 0:
+            raise ValueError("params.width must be positive and params.maxDepth >= 0")
+        flags = int(flags)
+        if flags & ~T.PATH_FLAGS:
+            raise ValueError("trace_paths takes only FLAG_REFERENCE_LAYOUT, FLAG_MEGAKERNEL, FLAG_STREAMED and FLAG_TREELETS, not %#x" % flags)
+        first_key = int(first_key)
+        if first_key < 0:
+            raise ValueError("first_key must be >= 0")
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (origins, dirs)]
+        if any(is_torch) and not all(is_torch):
+            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
+        if all(is_torch):
+            return self._trace_paths_torch(origins, dirs, params, first_key, flags, slot)
+        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
+        if slot is not None:
+            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        n = o.shape[0]
+        if first_key + n > 0x7FFFFFFF:
+            raise ValueError("first_key + n exceeds 2^31 - 1")
+        rays = np.zeros((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        out = np.zeros(n, T.np_dtype(T.PathResult))
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_paths(self._ctx, C.byref(params), flags, rays.ctypes.data if n else None, n, first_key,
+                                            out.ctypes.data if n else None, -1, C.byref(ms)))
+        self.last_query_ms = ms.value
+        return out
+
+    def _trace_paths_torch(self, origins, dirs, params, first_key, flags, slot):
+        import torch                                       # lazy: the host path needs no torch
+        for name, a in (("origins", origins), ("dirs", dirs)):
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
+            if a.device.type != "cuda":
+                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
+        if origins.shape != dirs.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
+        if origins.device != dirs.device:
+            raise ValueError("origins and dirs live on different devices")
+        n = origins.shape[0]
+        if first_key + n > 0x7FFFFFFF:
+            raise ValueError("first_key + n exceeds 2^31 - 1")
+        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+        slots = [i for i, d in enumerate(self.device_ids) if d == dev]
+        if slot is None:
+            if not slots:
+                raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
+            slot = slots[0]
+        elif slot not in slots:
+            raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
+        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
+        rays[:, 0:3], rays[:, 4:7] = origins, dirs
+        out = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
+        torch.cuda.synchronize(origins.device)               # the library works on its own streams
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_paths(self._ctx, C.byref(params), flags, rays.data_ptr() if n else None, n, first_key,
+                                            out.data_ptr() if n else None, slot, C.byref(ms)))
+        self.last_query_ms = ms.value
+        ints = out.view(torch.int32)
+        return dict(radiance=out[:, 0:3], color=ints[:, 3], depth=out[:, 4], objId=ints[:, 5])
+
+    @staticmethod
+    def camera_rays(params):
+        """The primary rays of the frame `params` describes (RTRay.cs:120-126, Ray.GenerateRay RTUtils.cs:13-17), in pixel order:
+        (origins, dirs) as (width*height, 3) float32, with pick's operation order, vectorised."""
+        cam = params.cam
+        f = np.float32
+        v3 = lambda a: np.array([a.X, a.Y, a.Z], np.float32)
+        w, h = int(params.width), int(params.height)
+        idx = np.arange(w * h, dtype=np.int64)
+        u = ((idx % max(1, w)).astype(np.float32) + f(0.5)) / f(max(1, w))
+        v = ((idx // max(1, w)).astype(np.float32) + f(0.5)) / f(max(1, h))
+        ll, hz, vt, org = v3(cam.lowerLeft), v3(cam.horizontal), v3(cam.vertical), v3(cam.origin)
+        d = ((ll[None, :] + hz[None, :] * u[:, None]) + vt[None, :] * v[:, None]) - org[None, :]
+        inv = f(1.0) / np.sqrt(np.maximum(f(1e-20), (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]))   # Normalize, Float3.cs:91-95
+        d = (d * inv[:, None]).astype(np.float32)
+        return np.broadcast_to(org, d.shape).astype(np.float32), d
 
     def pick(self, width, height, x, y):
         """The closest hit under pixel (x, y) of a width x height image (row 0 = bottom row): the pixel-centre primary ray of the

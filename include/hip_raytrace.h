@@ -32,6 +32,8 @@
  *                          reservoirs)                           Framebuffer.cs:60-97
  *   hrt_trace_rays         SceneDeviceViews.TraceClosest / ShadowOcclusion over caller rays
  *                                                                SceneDeviceViews.cs:30-121
+ *   hrt_trace_paths        PathTraceKernel over caller rays in place of camera rays
+ *                                                                RTRay.cs:187-199,203-325
  *   hrt_destroy            RTRenderer.Dispose                    RTRenderer.cs:347-363
  *   hrt_last_error         the exception message of CudaException / Argument*Exception
  *
@@ -327,6 +329,35 @@ enum hrt_ray_query { HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1 };
 #define HRT_QUERY_CHUNK (1 << 21)      /* rays per walk: a device slot works through its rays in chunks of at most this many */
 int  hrt_trace_rays(hrt_ctx* ctx, int32_t query, const hrt_ray* rays, int64_t n, void* results,
                     int32_t dev, float* device_ms);
+
+/* ---- radiance queries: PathTraceKernel (RTRay.cs:203-325) along caller rays on the scene now on the device.
+ * Ray i (0 <= i < n) has key j = first_key + i and RNG pixel (px, py) = (j % params->width, j / params->width).  It is shaded as
+ * that pixel of a frame with reuse off, with two substitutions:
+ *   - primary vertex: TraceClosest(ray) replaces the camera ray (RTRay.cs:187-199).  No tMax: hrt_ray.tMax and pad are ignored,
+ *     dir is used as given.  The vertex takes the frame's G-buffer encoding (packedMat = shade | FloatToI16(ior) << 16, so ior is
+ *     quantised as in a frame); a miss stores worldPos = origin + dir * 1e6f and objId = -1 (StoreMiss).
+ *   - camera-derived values take the ray's own origin and direction: ViewDirFromCam(pos) is normalize(pos - ray.origin), the miss
+ *     colour SkyWeighted(PrimaryRayDir(index)) is SkyWeighted(ray.dir) (added spp times, in order), DistanceFromCamera is
+ *     |worldPos - ray.origin|.
+ * Everything else is the frame's: frame, rngLockNoise, spp (max(1, spp)), maxDepth, the sun and sky tints, the RNG salt, the bounce
+ * loop, Russian roulette, the ReSTIR candidate stream with reuse off, SafeColor, the in-order sum and the final 1/spp scale.
+ * cam, prevCam, height and debugCamSeq are ignored; resCur and cameraId are not written.
+ * Camera rays in pixel order (o = cam.origin, d = normalize(lowerLeft + horizontal*u + vertical*v - origin)) with first_key = 0,
+ * the frame's width and reuse off give results[p] == the frame's radiance[p], color[p], depth[p], objectId[p], bit for bit.
+ *   - flags: HRT_FLAG_REFERENCE_LAYOUT, MEGAKERNEL, STREAMED, TREELETS only (any other bit: HRT_ERR_INVALID_ARG).  REFERENCE_LAYOUT
+ *     selects TracerRef as for a frame.  MEGAKERNEL, STREAMED and TREELETS are accepted and ignored: every query runs the fused
+ *     path-trace organisation (a frame forced to it with MEGAKERNEL costs the same; scenes whose frames stream are several times
+ *     slower as queries).  Results do not depend on the organisation.
+ *   - HRT_ERR_INVALID_ARG: enableTemporalReuse or enableSpatialReuse nonzero, width <= 0, maxDepth < 0, first_key < 0,
+ *     first_key + n > 2^31 - 1, NULL rays or results with n > 0.  HRT_ERR_INVALID_STATE: no scene uploaded.  n == 0 launches nothing.
+ *   - dev, device_ms: as hrt_trace_rays (dev < 0: host arrays over every device slot in bounded chunks through pinned staging or a
+ *     range registered with hrt_host_register; dev >= 0: device memory of that slot, 16-byte aligned).
+ *   - Blocking; runs on the device streams after any HRT_FLAG_NO_SYNC frames.  Frame state is left alone (G-buffer, reservoirs,
+ *     present history, hrt_frame_times, hrt_device_views pointers, a pending progressive frame): the query works in a private
+ *     per-chunk workspace freed by hrt_destroy. */
+int  hrt_trace_paths(hrt_ctx* ctx, const hrt_frame_params* params, uint32_t flags,
+                     const hrt_ray* rays, int64_t n, int64_t first_key,
+                     hrt_path_result* results, int32_t dev, float* device_ms);
 int  hrt_reset_history(hrt_ctx* ctx);           /* zero both reservoir sets */
 
 /* Test hooks (math probes, host-side builders of derived trees) are declared in hrt_test_hooks.h and exist only in

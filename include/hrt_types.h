@@ -218,7 +218,19 @@ typedef struct hrt_ray_hit {        /* 48 bytes: TraceClosest's out parameters p
     int32_t instance, prim;         /* instance record index; sphere index or triangle index (miss: -1 / -1)  */
 } hrt_ray_hit;
 
+/*
+ * Radiance queries (hrt_trace_paths): PathTraceKernel (RTRay.cs:203-325) for a caller ray in place of the camera ray.
+ */
+typedef struct hrt_path_result {    /* 32 bytes: two 16-byte stores                                             */
+    hrt_float3 radiance;            /* Lout: mean over spp of SafeColor(Li), pre-pack (RTRay.cs:319-323)        */
+    int32_t    color;               /* PackRGBA8(radiance) (RTRay.cs:66-76)                                     */
+    float      depth;               /* |worldPos - ray.origin|; miss: worldPos = origin + dir * 1e6f            */
+    int32_t    objId;               /* objId of the primary hit, -1 on a miss                                   */
+    int32_t    reserved[2];         /* written as 0                                                             */
+} hrt_path_result;
+
 HRT_STATIC_ASSERT(sizeof(hrt_ray) == 32, "hrt_ray is 32 bytes");
 HRT_STATIC_ASSERT(sizeof(hrt_ray_hit) == 48, "hrt_ray_hit is 48 bytes");
+HRT_STATIC_ASSERT(sizeof(hrt_path_result) == 32, "hrt_path_result is 32 bytes");
 
 #endif /* HRT_TYPES_H */
