@@ -69,6 +69,31 @@ namespace ILGPU_Raytracing.Engine
             return hit;
         }
 
+        /// <summary>The k nearest hits along each ray (hrt_trace_hits): hits[i * k + j], j &lt; counts[i], in ascending (t, instance, prim);
+        /// the remaining slots hold the miss record.  totals (optional, one per ray): every accepted hit of the ray.  Returns rays.Length.</summary>
+        public int TraceHits(ReadOnlySpan<HrtRay> rays, int k, Span<HrtRayHit> hits, Span<int> counts, Span<int> totals = default)
+        {
+            if (k < 1 || k > HipRaytrace.HRT_HITS_MAX) throw new ArgumentOutOfRangeException(nameof(k));
+            if (hits.Length < (long)rays.Length * k) throw new ArgumentException("hits is shorter than rays.Length * k");
+            if (counts.Length < rays.Length) throw new ArgumentException("counts is shorter than rays");
+            if (!totals.IsEmpty && totals.Length < rays.Length) throw new ArgumentException("totals is shorter than rays");
+            fixed (HrtRay* r = rays) fixed (HrtRayHit* h = hits) fixed (int* c = counts) fixed (int* t = totals)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_trace_hits(_ctx, r, rays.Length, k, h, c, totals.IsEmpty ? null : t, -1, null));
+            return rays.Length;
+        }
+
+        /// <summary>Picking through surfaces: the k nearest hits under pixel (x, y), nearest first, on the ray Pick casts.</summary>
+        public HrtRayHit[] PickAll(in Camera cam, int width, int height, int x, int y, int k)
+        {
+            float u = (x + 0.5f) / Math.Max(1, width), v = (y + 0.5f) / Math.Max(1, height);
+            Ray r = Ray.GenerateRay(cam, u, v);
+            var ray = new HrtRay { origin = r.origin, dir = r.dir, tMax = float.PositiveInfinity };
+            var hits = new HrtRayHit[k];
+            var counts = new int[1];
+            TraceHits(new ReadOnlySpan<HrtRay>(&ray, 1), k, hits, counts);
+            return hits.AsSpan(0, counts[0]).ToArray();
+        }
+
         /// <summary>Radiance along caller rays (hrt_trace_paths): ray i is path-traced as pixel key firstKey + i of the frame `p`
         /// describes (reuse off), with its own origin and direction in place of the camera's.  Panoramas, probes, custom cameras.
         /// The frame's own camera rays in pixel order give the frame's colour, radiance, depth and objectId bit for bit.</summary>

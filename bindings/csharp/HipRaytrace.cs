@@ -137,6 +137,10 @@ namespace ILGPU_Raytracing.Engine
         // (results: int[n] of 0/1).  dev < 0: host arrays, split over every device slot; dev >= 0: device pointers of that slot.  Blocking.
         public const int HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1;
         [DllImport(Lib)] public static extern int hrt_trace_rays(IntPtr ctx, int query, HrtRay* rays, long n, void* results, int dev, float* deviceMs);
+        // the k nearest accepted hits along each ray (k <= HRT_HITS_MAX): hits[i * k + j] for j < counts[i], CLOSEST's miss record after;
+        // totals (may be null): every accepted test of ray i.  Arguments, devices and blocking as hrt_trace_rays.
+        public const int HRT_HITS_MAX = 16;
+        [DllImport(Lib)] public static extern int hrt_trace_hits(IntPtr ctx, HrtRay* rays, long n, int k, HrtRayHit* hits, int* counts, int* totals, int dev, float* deviceMs);
         [DllImport(Lib)] public static extern int hrt_trace_paths(IntPtr ctx, HrtFrameParams* p, uint flags, HrtRay* rays, long n, long firstKey, HrtPathResult* results, int dev, float* deviceMs);
 
         // native asset loader (optional: a C# host may keep MeshLoaderOBJ)

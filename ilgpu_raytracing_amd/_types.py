@@ -183,6 +183,7 @@ assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PathResult) =
 
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1      # hrt_ray_query
 QUERY_CHUNK = 1 << 21                     # HRT_QUERY_CHUNK: rays per walk of one device slot (and keys per radiance-query chunk)
+HITS_MAX = 16                             # HRT_HITS_MAX: largest k of hrt_trace_hits (the k nearest hits per ray)
 PATH_FLAGS = 4 | 16 | 32 | 256            # REFERENCE_LAYOUT | MEGAKERNEL | STREAMED | TREELETS: the flags hrt_trace_paths takes
 
 

@@ -27,6 +27,7 @@
 #include "hrt_post.hpp"
 #include "hrt_query.hpp"
 #include "hrt_paths.hpp"
+#include "hrt_hits.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
 #include "../../include/hrt_test_hooks.h"
@@ -567,6 +568,10 @@ struct DeviceState {
     // radiance queries (hrt_trace_paths): rays and results are staged through q_mem / q_host; the chunk's G-buffer planes (48 B per slot)
     // and the scratch planes of sample groups live here, never in the frame's buffers
     void* p_mem = nullptr; size_t p_bytes = 0;
+    // multi-hit queries (hrt_trace_hits): private device workspace of one chunk (hand-out counters, and on the host path the staged
+    // rays, hit slots, counts and totals) and its pinned host staging; grown on demand, freed with the rest of the query state
+    void* h_mem = nullptr; size_t h_bytes = 0;
+    void* h_host = nullptr; size_t h_host_bytes = 0;
 };
 
 } // namespace
@@ -1604,6 +1609,9 @@ void free_query(DeviceState& d)
     d.q_mem = nullptr; d.q_host = nullptr; d.q_cap = d.q_host_cap = 0;
     if (d.p_mem) (void)hipFree(d.p_mem);
     d.p_mem = nullptr; d.p_bytes = 0;
+    if (d.h_mem) (void)hipFree(d.h_mem);
+    if (d.h_host) (void)hipHostFree(d.h_host);
+    d.h_mem = nullptr; d.h_host = nullptr; d.h_bytes = d.h_host_bytes = 0;
 }
 
 // device staging for m rays (and the pinned host staging too when `host`); the caller has made d's device current
@@ -1724,6 +1732,105 @@ int query_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const h
         HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
         *ms += t;
         if (!dev_ptrs && !resReg) std::memcpy(dst, hostRes, (size_t)m * resBytes);
+    }
+    return HRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Multi-hit queries (hrt_trace_hits, kernels in hrt_hits.hip).  A chunk holds at most kQueryChunk hit slots (rays * k), so the staging
+// does not grow with k.  The walk keeps each ray's candidates in the ray's own hit slots and the finish shades them in place: the
+// device workspace is the 8 hand-out counters, plus the staged rays, hit slots, counts and totals on the host path.
+// ---------------------------------------------------------------------------------------
+constexpr size_t kHitsGrabBytes = 8 * kQueryGrabStride * sizeof(int);
+
+int ensure_hits(hrt_ctx* c, DeviceState& d, size_t devBytes, size_t hostBytes)
+{
+    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
+    if (d.h_bytes < devBytes)
+    {
+        if (d.h_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.h_mem); d.h_mem = nullptr; d.h_bytes = 0; }
+        HIPCHK(c, hipMalloc(&d.h_mem, devBytes));
+        d.h_bytes = devBytes;
+    }
+    if (hostBytes && d.h_host_bytes < hostBytes)
+    {
+        if (d.h_host) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipHostFree(d.h_host); d.h_host = nullptr; d.h_host_bytes = 0; }
+        HIPCHK(c, hipHostMalloc(&d.h_host, hostBytes, hipHostMallocPortable));
+        d.h_host_bytes = hostBytes;
+    }
+    return HRT_OK;
+}
+
+// rays [begin, end) of one device slot, chunk by chunk on the slot's main stream (after any frame in flight): H2D of the rays, walk,
+// finish, fix-up, D2H of hits, counts and totals.  dev_ptrs: the arrays are device memory of this slot.  *ms += kernel time.
+int hits_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_ray* rays, int k, hrt_ray_hit* hits,
+              int32_t* counts, int32_t* totals, int64_t begin, int64_t end, bool dev_ptrs, float* ms)
+{
+    HIPCHK(c, hipSetDevice(d.device_id));
+    auto registered = [&](const void* p, size_t bytes) {
+        for (const auto& r : cc.pinned) if ((const char*)p >= r.first && (const char*)p + bytes <= r.first + r.second) return true;
+        return false;
+    };
+    const hipStream_t st = d.stream;
+    const int64_t per = std::max<int64_t>(1, kQueryChunk / k);          // rays per chunk: at most kQueryChunk hit slots
+    const int64_t cap = std::min<int64_t>(per, end - begin);
+    const size_t raysB = (size_t)cap * sizeof(hrt_ray), hitsB = (size_t)cap * k * sizeof(hrt_ray_hit), intsB = (size_t)cap * sizeof(int32_t);
+    int rc = ensure_hits(c, d, kHitsGrabBytes + (dev_ptrs ? 0 : raysB + hitsB + 2 * intsB), dev_ptrs ? 0 : raysB + hitsB + 2 * intsB);
+    if (rc != HRT_OK) return rc;
+    char* dbase = (char*)d.h_mem;
+    char* hbase = (char*)d.h_host;
+    for (int64_t off = begin; off < end; off += per)
+    {
+        const int64_t m = std::min<int64_t>(per, end - off);
+        HitsLaunch L;
+        L.variant = cc.packed_ok ? cc.packed_feat : -1;
+        L.lt3 = cc.packed_feat != 0 && d.dpacked.leafTris == 3;
+        L.S = d.dscene; L.P = d.dpacked;
+        HitsK& h = L.h;
+        h.grab = (int*)dbase;
+        h.n = (int)m; h.k = k; h.nSegs = (int)((m + kQuerySeg - 1) / kQuerySeg);
+        L.gridW = (unsigned)std::min<long long>((h.nSegs + 3) / 4, (long long)d.n_cu * kWalkBlocksPerCU);     // persistent waves, as hrt_trace_rays
+        const hrt_ray* src = rays + off;
+        hrt_ray_hit* dHits = hits + (size_t)off * k;
+        int32_t* dCounts = counts + off;
+        int32_t* dTotals = totals ? totals + off : nullptr;
+        const size_t mRays = (size_t)m * sizeof(hrt_ray), mHits = (size_t)m * k * sizeof(hrt_ray_hit), mInts = (size_t)m * sizeof(int32_t);
+        const bool rayReg = !dev_ptrs && registered(src, mRays);
+        const bool hitReg = !dev_ptrs && registered(dHits, mHits);
+        const bool cntReg = !dev_ptrs && registered(dCounts, mInts);
+        const bool totReg = !dev_ptrs && dTotals && registered(dTotals, mInts);
+        char* sRays = hbase; char* sHits = hbase + raysB; char* sCounts = sHits + hitsB; char* sTotals = sCounts + intsB;
+        if (dev_ptrs)
+        {
+            h.rays = (const float4*)src; h.hits = (float4*)dHits; h.counts = dCounts; h.totals = dTotals;
+        }
+        else
+        {
+            char* p = dbase + kHitsGrabBytes;
+            h.rays = (const float4*)p; h.hits = (float4*)(p + raysB); h.counts = (int32_t*)(p + raysB + hitsB);
+            h.totals = dTotals ? (int32_t*)(p + raysB + hitsB + intsB) : nullptr;
+            if (!rayReg) std::memcpy(sRays, src, mRays);
+            HIPCHK(c, hipMemcpyAsync((void*)h.rays, rayReg ? (const void*)src : (const void*)sRays, mRays, hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
+        HIPCHK(c, hits_launch(L, st));
+        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
+        if (!dev_ptrs)
+        {
+            HIPCHK(c, hipMemcpyAsync(hitReg ? (void*)dHits : (void*)sHits, h.hits, mHits, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(cntReg ? (void*)dCounts : (void*)sCounts, h.counts, mInts, hipMemcpyDeviceToHost, st));
+            if (dTotals) HIPCHK(c, hipMemcpyAsync(totReg ? (void*)dTotals : (void*)sTotals, h.totals, mInts, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(c, hipStreamSynchronize(st));
+        float t = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
+        *ms += t;
+        if (!dev_ptrs)
+        {
+            if (!hitReg) std::memcpy(dHits, sHits, mHits);
+            if (!cntReg) std::memcpy(dCounts, sCounts, mInts);
+            if (dTotals && !totReg) std::memcpy(dTotals, sTotals, mInts);
+        }
     }
     return HRT_OK;
 }
@@ -3234,6 +3341,66 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_trace_rays"); }
+
+int hrt_trace_hits(hrt_ctx* c, const hrt_ray* rays, int64_t n, int32_t k, hrt_ray_hit* hits, int32_t* counts, int32_t* totals,
+                   int32_t dev, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (k < 1 || k > HRT_HITS_MAX) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: k must be in [1, HRT_HITS_MAX]");
+    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: n must be >= 0");
+    if (n > 0 && (!rays || !hits || !counts)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: rays, hits and counts are needed when n > 0");
+    const int nd = (int)c->dev.size();
+    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: device slot out of range");
+    if (n == 0) return HRT_OK;
+    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_hits: no scene uploaded (call hrt_scene_upload first)");
+    const size_t hitsB = (size_t)n * (size_t)k * sizeof(hrt_ray_hit), intsB = (size_t)n * sizeof(int32_t);
+    if (dev >= 0)
+    {
+        DeviceState& d = c->dev[(size_t)dev];
+        HIPCHK(c, hipSetDevice(d.device_id));
+        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, hits, hitsB) || !on_device(d, counts, intsB) ||
+            (totals && !on_device(d, totals, intsB)))
+            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: with dev >= 0, rays, hits, counts and totals must be device memory of that slot's device, large enough for n");
+        if ((((uintptr_t)rays | (uintptr_t)hits) & 15) || (((uintptr_t)counts | (uintptr_t)totals) & 3))
+            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: device rays and hits must be 16-byte aligned, counts and totals 4-byte aligned");
+        float ms = 0.f;
+        int rc = hits_slot(c, *c, d, rays, k, hits, counts, totals, 0, n, true, &ms);
+        if (rc != HRT_OK) return rc;
+        if (device_ms) *device_ms = ms;
+        return HRT_OK;
+    }
+    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as hrt_trace_rays)
+    if (in_device_memory(rays) || in_device_memory(hits) || in_device_memory(counts) || (totals && in_device_memory(totals)))
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: with dev < 0, rays, hits, counts and totals must be host memory (pass the slot of device pointers as dev)");
+    std::vector<float> ms((size_t)nd, 0.f);
+    auto part = [&](int i) { return n * i / nd; };
+    if (nd > 1)
+    {
+        std::vector<int> rcs((size_t)nd, HRT_OK);
+        std::vector<std::string> errs((size_t)nd);
+        std::vector<std::thread> workers;
+        for (int i = 0; i < nd; i++)
+            workers.emplace_back([&, i]() {
+                try
+                {
+                    rcs[(size_t)i] = hits_slot(nullptr, *c, c->dev[(size_t)i], rays, k, hits, counts, totals, part(i), part(i + 1), false, &ms[(size_t)i]);
+                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
+                }
+                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
+            });
+        for (std::thread& t : workers) t.join();
+        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_hits: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
+    }
+    else
+    {
+        int rc = hits_slot(c, *c, c->dev[0], rays, k, hits, counts, totals, 0, n, false, &ms[0]);
+        if (rc != HRT_OK) return rc;
+    }
+    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_trace_hits"); }
 
 // hrt_trace_paths: rays [begin, end) of one device slot, chunk by chunk on the slot's main stream (after any frame in flight): H2D of the
 // rays, primary kernel into the private G-buffer, fused path stage writing the result records, D2H.  A chunk is whole rows of width

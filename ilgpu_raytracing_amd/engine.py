@@ -66,6 +66,8 @@ def _load(path, hooks=False):
     L.hrt_host_unregister.argtypes = [C.c_void_p, C.c_void_p]
     L.hrt_set_workspace_limit.argtypes = [C.c_void_p, C.c_int64]
     L.hrt_trace_rays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+    L.hrt_trace_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.POINTER(C.c_float)]
     L.hrt_trace_paths.argtypes = [C.c_void_p, C.POINTER(T.FrameParams), C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                   C.c_int32, C.POINTER(C.c_float)]
     L.hrt_device_count.restype = C.c_int
@@ -716,6 +718,85 @@ class RTRenderer(FrameHost):
         ints = out[:, 8:12].view(torch.int32)
         return dict(t=out[:, 0], normal=out[:, 1:4], albedo=out[:, 4:7], ior=out[:, 7],
                     objId=ints[:, 0], shade=ints[:, 1], instance=ints[:, 2], prim=ints[:, 3])
+
+    def trace_hits(self, origins, dirs, k, tmax=None, totals=False, slot=None):
+        """The k nearest accepted hits along each ray (hrt_trace_hits): ShadowOcclusion's walk (SceneDeviceViews.cs:89-121) run to the
+        end with TraceClosest's acceptance and records (:30-86, :124-237), ordered by (t, instance, prim).  origins, dirs: (n, 3) float32,
+        dirs used as given.  k: 1..T.HITS_MAX.  tmax: a float or (n,) float32 (default +inf).  totals: also return every accepted test.
+        numpy inputs: host path over every device slot; returns (hits, counts, totals or None), hits an (n, k) structured array of
+        T.RayHit (slots j >= counts[i] hold CLOSEST's miss record).
+        torch tensors on a GPU: device path on the slot of their device; returns a dict of tensors t, normal, albedo, ior (float32),
+        objId, shade, instance, prim (int32), each (n, k, ...), plus counts (n,) and totals ((n,) or None)."""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise TypeError("k must be an int, not %r" % (k,))
+        k = int(k)
+        if not 1 <= k <= T.HITS_MAX:
+            raise ValueError("k must be in [1, %d], got %d" % (T.HITS_MAX, k))
+        totals = bool(totals)
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (origins, dirs)]
+        if any(is_torch) and not all(is_torch):
+            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
+        if all(is_torch):
+            return self._trace_hits_torch(origins, dirs, k, tmax, totals, slot)
+        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
+        if slot is not None:
+            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        n = o.shape[0]
+        rays = np.zeros((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        rays[:, 3] = _tmax_arg(tmax, n)
+        hits = np.zeros((n, k), T.np_dtype(T.RayHit))
+        counts = np.zeros(n, np.int32)
+        tot = np.zeros(n, np.int32) if totals else None
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_hits(self._ctx, rays.ctypes.data if n else None, n, k, hits.ctypes.data if n else None,
+                                           counts.ctypes.data if n else None, tot.ctypes.data if (n and totals) else None, -1, C.byref(ms)))
+        self.last_query_ms = ms.value
+        return hits, counts, tot
+
+    def _trace_hits_torch(self, origins, dirs, k, tmax, totals, slot):
+        import torch
+        for name, a in (("origins", origins), ("dirs", dirs)):
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
+            if a.device.type != "cuda":
+                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
+        if origins.shape != dirs.shape:
+            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
+        if origins.device != dirs.device:
+            raise ValueError("origins and dirs live on different devices")
+        n = origins.shape[0]
+        if not (tmax is None or isinstance(tmax, (int, float, np.floating))):
+            tm = torch.as_tensor(tmax, device=origins.device)
+            if tm.dtype != torch.float32 or tuple(tm.shape) != (n,):
+                raise ValueError("tmax must be a float or an (n,) float32 array")
+        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+        slots = [i for i, d in enumerate(self.device_ids) if d == dev]
+        if slot is None:
+            if not slots:
+                raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
+            slot = slots[0]
+        elif slot not in slots:
+            raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
+        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
+        rays[:, 0:3], rays[:, 4:7] = origins, dirs
+        if tmax is None or isinstance(tmax, (int, float, np.floating)):
+            rays[:, 3] = float("inf") if tmax is None else float(np.float32(tmax))
+        else:
+            rays[:, 3] = tm
+        out = torch.zeros((n, k, 12), dtype=torch.float32, device=origins.device)
+        counts = torch.zeros(n, dtype=torch.int32, device=origins.device)
+        tot = torch.zeros(n, dtype=torch.int32, device=origins.device) if totals else None
+        torch.cuda.synchronize(origins.device)               # the library works on its own streams
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_trace_hits(self._ctx, rays.data_ptr() if n else None, n, k, out.data_ptr() if n else None,
+                                           counts.data_ptr() if n else None, tot.data_ptr() if (n and totals) else None, slot, C.byref(ms)))
+        self.last_query_ms = ms.value
+        ints = out[:, :, 8:12].view(torch.int32)
+        return dict(t=out[:, :, 0], normal=out[:, :, 1:4], albedo=out[:, :, 4:7], ior=out[:, :, 7],
+                    objId=ints[:, :, 0], shade=ints[:, :, 1], instance=ints[:, :, 2], prim=ints[:, :, 3], counts=counts, totals=tot)
 
     def trace_paths(self, origins, dirs, params, first_key=0, flags=0, slot=None):
         """PathTraceKernel (RTRay.cs:203-325) along caller rays (hrt_trace_paths): ray i is shaded as pixel key j = first_key + i of

@@ -32,6 +32,8 @@
  *                          reservoirs)                           Framebuffer.cs:60-97
  *   hrt_trace_rays         SceneDeviceViews.TraceClosest / ShadowOcclusion over caller rays
  *                                                                SceneDeviceViews.cs:30-121
+ *   hrt_trace_hits         the k nearest accepted hits along caller rays (ShadowOcclusion's walk, TraceClosest's records)
+ *                                                                SceneDeviceViews.cs:30-237
  *   hrt_trace_paths        PathTraceKernel over caller rays in place of camera rays
  *                                                                RTRay.cs:187-199,203-325
  *   hrt_destroy            RTRenderer.Dispose                    RTRenderer.cs:347-363
@@ -328,6 +330,34 @@ int  hrt_device_buffers(hrt_ctx* ctx, int dev, hrt_device_views* out);
 enum hrt_ray_query { HRT_QUERY_CLOSEST = 0, HRT_QUERY_OCCLUDED = 1 };
 #define HRT_QUERY_CHUNK (1 << 21)      /* rays per walk: a device slot works through its rays in chunks of at most this many */
 int  hrt_trace_rays(hrt_ctx* ctx, int32_t query, const hrt_ray* rays, int64_t n, void* results,
+                    int32_t dev, float* device_ms);
+
+/* ---- multi-hit queries: the k nearest accepted primitive tests along each caller ray, on the scene now on the device.
+ * Defined by an unpruned walk of the uploaded tree with ShadowOcclusion's limits and TraceClosest's per-hit records:
+ *   - TLAS: IntersectAABB(ray, box, 0.001f, ray.tMax); every leaf entry reached transforms the ray (TransformRay(worldToObject)),
+ *     scale = uniformScale > 0 ? uniformScale : 1, tMaxObj = tMax * scale (SceneDeviceViews.cs:89-121).
+ *   - BLAS: IntersectAABB(rayObj, box, 0.001f, tMaxObj).  A primitive test is accepted when the intersection routine reports a hit
+ *     with t > 0.001f && t < tMaxObj; a triangle must also pass TraceClosest's alpha rule, linear mask sample >= AlphaCutoff
+ *     (:206-221; not AnyHit's point/band rule).
+ *   - One record per accepted test: the hrt_ray_hit CLOSEST would return if that hit won (:65-86, :146-159, :196-227): t = tObj / scale,
+ *     normal = Normalize(TransformVector(objectToWorld, nObj)) with the TwoSided flip in object space, the sphere albedo rules (Kd or
+ *     albedo, texture by atan2/acos) or the triangle's Kd or diffuse texture, objId (triangle index, -1 for a sphere), shade, ior
+ *     (s.ior > 0 ? s.ior : 1; 1 for triangles), instance = the instance record, prim = the sphere or triangle index.
+ *   - Order: ascending t as IEEE totalOrder (t >= +0 or NaN: the unsigned bit pattern), then instance, then prim.  A tree that lists
+ *     a primitive or an instance twice gives identical duplicate records, side by side.
+ * hits: n * k records, hits[i * k + j]; slots j >= counts[i] hold CLOSEST's miss record (t = 1e30, normal 0, albedo 1, ior 1,
+ *   objId -1, shade 0, instance -1, prim -1).  counts[i] = min(k, totals[i]).  Hits at t >= 1e29 are hits.
+ * totals (may be NULL): every accepted test of ray i, saturating at INT32_MAX.  No box test is cut at the k-th distance (no such
+ *   cut is provably exact in float arithmetic), so results with and without totals are the same bit for bit.
+ * Any float tMax is legal (0, negative, NaN, +-inf): what the slab and t tests make of it.  hrt_ray.pad is ignored.
+ * HRT_ERR_INVALID_ARG: k < 1 or k > HRT_HITS_MAX, n < 0, NULL rays, hits or counts with n > 0, a bad slot or memory kind,
+ *   misalignment.  HRT_ERR_INVALID_STATE: no scene uploaded.  n == 0 launches nothing.
+ * dev, device_ms, blocking and frame state: as hrt_trace_rays.  dev < 0 chunks by hit slots (at most HRT_QUERY_CHUNK of n * k per
+ *   chunk); dev >= 0 takes device memory of that slot, rays and hits 16-byte aligned, counts and totals 4-byte aligned.  The query
+ *   works in a private workspace freed by hrt_destroy and leaves the frame's state and a pending progressive frame alone. */
+#define HRT_HITS_MAX 16
+int  hrt_trace_hits(hrt_ctx* ctx, const hrt_ray* rays, int64_t n, int32_t k,
+                    hrt_ray_hit* hits, int32_t* counts, int32_t* totals,
                     int32_t dev, float* device_ms);
 
 /* ---- radiance queries: PathTraceKernel (RTRay.cs:203-325) along caller rays on the scene now on the device.
