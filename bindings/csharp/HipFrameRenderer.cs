@@ -36,6 +36,15 @@ namespace ILGPU_Raytracing.Engine
             return Present(outW, outH, taau);
         }
 
+        /// <summary>Render with the present mode spelled out: HrtPresentMode.TaauReproject reads the TAAU history where the camera's
+        /// motion since the last resolved frame puts it (the reprojection RTTaa.ResolveUpsample declares and leaves out).</summary>
+        public ReadOnlySpan<int> Render(in HrtFrameParams frame, int outW, int outH, HrtPresentMode mode)
+        {
+            fixed (HrtFrameParams* fp = &frame)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_render_frame(_ctx, fp, null, null, null));
+            return Present(outW, outH, mode);
+        }
+
         /// <summary>One step of a progressive frame: samples [sampleBegin, frame.spp) of the frame, then the same presentation as
         /// Render.  sampleBegin 0 starts the frame; a later step passes the same frame with a larger spp and sampleBegin = the spp of
         /// the step before.  The returned preview is what Render(frame) would return at frame.spp samples, and the last step's is the
@@ -47,13 +56,27 @@ namespace ILGPU_Raytracing.Engine
             return Present(outW, outH, taau);
         }
 
-        private ReadOnlySpan<int> Present(int outW, int outH, bool taau)
+        private ReadOnlySpan<int> Present(int outW, int outH, bool taau) => Present(outW, outH, taau ? HrtPresentMode.Taau : HrtPresentMode.Resample);
+
+        /// <summary>Presents the last frame again (or for the first time) with the given mode; the history follows the frames that
+        /// were actually resolved, so skipping or repeating a present is safe in every mode.</summary>
+        public ReadOnlySpan<int> Present(int outW, int outH, HrtPresentMode mode)
         {
             if (_display.Length != outW * outH) _display = new int[outW * outH];
-            var pp = new HrtPresentParams { out_width = outW, out_height = outH, mode = taau ? 1 : 0 };   // tunables <= 0: the reference's 0.075 / 0.10 / 1.25
+            var pp = new HrtPresentParams { out_width = outW, out_height = outH, mode = (int)mode };   // tunables <= 0: the reference's 0.075 / 0.10 / 1.25
             fixed (int* dst = _display)
                 HipRaytrace.Check(_ctx, HipRaytrace.hrt_present(_ctx, &pp, dst));
             return _display;
+        }
+
+        /// <summary>Camera motion vectors of the last full-image frame (hrt_motion_vectors), one per internal pixel, in pixels: where the
+        /// pixel's surface point was in fromCam's image minus where it is now; NaN where the point is behind either camera.
+        /// fromCam null: the frame's prevCam.</summary>
+        public void MotionVectors(Span<Float2> mv, Camera? fromCam = null)
+        {
+            Camera cam = fromCam.GetValueOrDefault();
+            fixed (Float2* dst = mv)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_motion_vectors(_ctx, fromCam.HasValue ? &cam : null, dst, -1, null));
         }
 
         /// <summary>Picking: the closest hit under pixel (x, y) of a width x height frame (row 0 = bottom row) seen through `cam`, the

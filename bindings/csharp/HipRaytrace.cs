@@ -50,7 +50,8 @@ namespace ILGPU_Raytracing.Engine
     public struct HrtRenderOpts { public uint flags; public int row_begin, row_end, strip_n, strip_i; }
 
     [StructLayout(LayoutKind.Sequential)]
-    public struct HrtPresentParams { public int out_width, out_height, mode; public float feedback, sharpness, clampK; }   // mode 0 blit / bilinear, 1 TAAU
+    public struct HrtPresentParams { public int out_width, out_height, mode; public float feedback, sharpness, clampK; }   // mode: HrtPresentMode
+    public enum HrtPresentMode { Resample = 0, Taau = 1, TaauReproject = 2 }   // hrt_present_mode: blit / bilinear, TAAU, TAAU with camera reprojection
 
     [StructLayout(LayoutKind.Sequential)]
     public unsafe struct HrtOutputs               // host destinations of one frame, any may be null
@@ -124,6 +125,9 @@ namespace ILGPU_Raytracing.Engine
         // sampleBegin 0 starts a frame, > 0 continues the last one (same params except spp, sampleBegin = its spp; hrt_present may run between)
         [DllImport(Lib)] public static extern int hrt_render_progressive(IntPtr ctx, HrtFrameParams* p, HrtRenderOpts* opts, int sampleBegin, HrtOutputs* outputs, HrtStats* stats);
         [DllImport(Lib)] public static extern int hrt_present(IntPtr ctx, HrtPresentParams* p, int* outColorHost);
+        [DllImport(Lib)] public static extern int hrt_present_time(IntPtr ctx, float* ms);
+        // camera motion vectors of the last full-image frame, in pixels; fromCam null: the frame's prevCam; dev < 0 host memory, 0 device memory of slot 0
+        [DllImport(Lib)] public static extern int hrt_motion_vectors(IntPtr ctx, Camera* fromCam, Float2* mv, int dev, float* deviceMs);
         [DllImport(Lib)] public static extern int hrt_synchronize(IntPtr ctx, HrtStats* stats);
         [DllImport(Lib)] public static extern int hrt_reset_history(IntPtr ctx);
         // page-lock the managed framebuffer arrays once (GCHandle.Alloc(array, GCHandleType.Pinned).AddrOfPinnedObject()): gathers

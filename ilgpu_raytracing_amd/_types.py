@@ -162,7 +162,7 @@ class PresentParams(C.Structure):
                 ("feedback", C.c_float), ("sharpness", C.c_float), ("clampK", C.c_float)]
 
 
-PRESENT_RESAMPLE, PRESENT_TAAU = 0, 1
+PRESENT_RESAMPLE, PRESENT_TAAU, PRESENT_TAAU_REPROJECT = 0, 1, 2      # hrt_present_mode
 
 
 class Ray(C.Structure):               # hrt_ray: a ray of hrt_trace_rays

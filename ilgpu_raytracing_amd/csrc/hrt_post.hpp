@@ -49,7 +49,51 @@ HRT_D F3 sample_catrom_srgb(const float* lut, const int32_t* a, int w, int h, fl
     return catrom(catrom(c00, c10, fx), catrom(c01, c11, fx), fy);
 }
 
-HRT_D void taa_resolve_pixel(const float* lut, const TaaK& p, int idx)                                 // :117-171
+// ---- camera reprojection (HRT_PRESENT_TAAU_REPROJECT, hrt_motion_vectors).  The reference declares it and leaves
+// it out (RTTaa.cs:49-57,82-84); the projection is its own ReprojectToPrevPixel (RTRay.cs:339-360) stopped before the (int) casts.
+// A camera is wave-uniform: it travels as a kernel argument (SGPRs) with tan(0.5 * fovY) evaluated once, on the host (hrt_tan is
+// bit-equal on both sides).  Nothing else is regrouped: z is per pixel, so x / (z * tanHalfFov * aspect) keeps its order.
+struct ProjCam { hrt_float3 origin, right, up, forward; float tanHalfFov, aspect; };
+struct Proj { bool ok; float fx, fy; };
+HRT_D Proj project_to_pixel(const ProjCam& c, F3 posWS, float width, float height)
+{
+    F3 p = posWS - cv3(c.origin);
+    float x = dot(p, cv3(c.right));
+    float y = dot(p, cv3(c.up));
+    float z = dot(p, cv3(c.forward));
+    Proj r;
+    r.ok = z > 1e-4f;
+    float ndcX = x / (z * c.tanHalfFov * c.aspect);
+    float ndcY = y / (z * c.tanHalfFov);
+    r.fx = 0.5f * (ndcX + 1.f) * width;
+    r.fy = 0.5f * (ndcY + 1.f) * height;
+    return r;
+}
+// where the surface point seen now was in the history camera's image, relative to where it is now: both projections run the same
+// expressions, so a bitwise equal camera gives (0, 0) exactly wherever the projection is finite
+struct Motion { bool ok; float dx, dy; };
+HRT_D Motion camera_motion(const ProjCam& hist, const ProjCam& cur, F3 posWS, float width, float height)
+{
+    Proj h = project_to_pixel(hist, posWS, width, height), c = project_to_pixel(cur, posWS, width, height);
+    Motion m;
+    m.ok = h.ok && c.ok; m.dx = h.fx - c.fx; m.dy = h.fy - c.fy;
+    return m;
+}
+HRT_D F3 ld3(const hrt_float3* a, int i) { return mk3(a[i].X, a[i].Y, a[i].Z); }
+// what the REPROJECT resolve reads besides TaaK: the frame's world positions and the history pair of the previous resolve (TaaK's
+// pair is the one written: a lane reads texels other lanes write, so the two are distinct and swapped after the launch)
+struct TaaReprojK { const hrt_float3* worldPos; const int32_t* prevColor; const int32_t* prevObjId; ProjCam histCam, curCam; };
+
+HRT_D void motion_vector_pixel(const hrt_float3* worldPos, const ProjCam& from, const ProjCam& cur, int width, int height, hrt_float2* mv, int idx)
+{
+    Motion m = camera_motion(from, cur, ld3(worldPos, idx), (float)width, (float)height);
+    const float nan = __builtin_nanf("");
+    hrt_float2 v; v.X = m.ok ? m.dx : nan; v.Y = m.ok ? m.dy : nan;
+    mv[idx] = v;
+}
+
+template <bool REPROJECT>
+HRT_D void taa_resolve_pixel(const float* lut, const TaaK& p, const TaaReprojK* rp, int idx)           // :117-171
 {
     const int outW = p.outW;
     int px = idx % outW, py = idx / outW;
@@ -69,9 +113,29 @@ HRT_D void taa_resolve_pixel(const float* lut, const TaaK& p, int idx)          
         }
     int ix = iclampi(hrt_f2i(hrt_round(sx)), 0, p.inW - 1), iy = iclampi(hrt_f2i(hrt_round(sy)), 0, p.inH - 1);   // SampleNearestObj :197-202
     int objId = p.inObjIdLow[iy * p.inW + ix];
-    F3 hist = unpack_srgb(lut, p.historyColor[idx]);
-    int histObj = p.historyObjId[idx];
-    bool reset = (p.isFirstFrame != 0) || (histObj != objId);
+    F3 hist; int histObj; bool reset;
+    if constexpr (REPROJECT)
+    {   // the history of the surface point under this pixel: bilinear in linear space at (px, py) + motion, objId of the nearer tap
+        Motion m = camera_motion(rp->histCam, rp->curCam, ld3(rp->worldPos, iy * p.inW + ix), (float)outW, (float)p.outH);
+        float qx = (float)px + m.dx, qy = (float)py + m.dy;
+        bool valid = m.ok && qx >= 0.f && qx <= (float)(outW - 1) && qy >= 0.f && qy <= (float)(p.outH - 1);   // a NaN fails every comparison
+        if (!valid) { qx = (float)px; qy = (float)py; }           // taps stay inside the image; reset makes the value irrelevant
+        float x0f = hrt_floor(qx), y0f = hrt_floor(qy);
+        float fx = qx - x0f, fy = qy - y0f;
+        int x0 = hrt_f2i(x0f), y0 = hrt_f2i(y0f);
+        int x1 = hrt_imin(x0 + 1, outW - 1), y1 = hrt_imin(y0 + 1, p.outH - 1);
+        F3 c00 = unpack_srgb(lut, rp->prevColor[y0 * outW + x0]), c10 = unpack_srgb(lut, rp->prevColor[y0 * outW + x1]);
+        F3 c01 = unpack_srgb(lut, rp->prevColor[y1 * outW + x0]), c11 = unpack_srgb(lut, rp->prevColor[y1 * outW + x1]);
+        hist = (c00 * (1.f - fx) + c10 * fx) * (1.f - fy) + (c01 * (1.f - fx) + c11 * fx) * fy;
+        histObj = rp->prevObjId[(fy < 0.5f ? y0 : y1) * outW + (fx < 0.5f ? x0 : x1)];
+        reset = (p.isFirstFrame != 0) || !valid || (histObj != objId);
+    }
+    else
+    {
+        hist = unpack_srgb(lut, p.historyColor[idx]);
+        histObj = p.historyObjId[idx];
+        reset = (p.isFirstFrame != 0) || (histObj != objId);
+    }
     // Clamp (:187-194): lo - k*0, hi + k*0
     F3 cmin = mk3(nmin.x - p.clampK * 0.0f, nmin.y - p.clampK * 0.0f, nmin.z - p.clampK * 0.0f);
     F3 cmax = mk3(nmax.x + p.clampK * 0.0f, nmax.y + p.clampK * 0.0f, nmax.z + p.clampK * 0.0f);

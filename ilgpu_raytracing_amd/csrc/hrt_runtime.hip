@@ -368,7 +368,31 @@ hrt_taa_resolve_kernel(TaaK p)
     lut[threadIdx.x] = srgb_to_linear_byte((int)threadIdx.x);
     __syncthreads();
     const int total = p.outW * p.outH;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) taa_resolve_pixel(lut, p, idx);
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) taa_resolve_pixel<false>(lut, p, nullptr, idx);
+}
+
+// HRT_PRESENT_TAAU_REPROJECT: the REPROJECT instantiation of the same resolve; reads the history pair in r, writes the pair in p
+__global__ void __launch_bounds__(256)
+hrt_taa_resolve_reproject_kernel(TaaK p, TaaReprojK r)
+{
+    __shared__ float lut[256];
+    lut[threadIdx.x] = srgb_to_linear_byte((int)threadIdx.x);
+    __syncthreads();
+    const int total = p.outW * p.outH;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) taa_resolve_pixel<true>(lut, p, &r, idx);
+}
+
+// hrt_motion_vectors: one lane per pixel of the nRows rows a device slot owns (8-row strips s of [rowBegin, rowEnd) with
+// s % stripN == stripI, in order); mv is indexed by the global pixel index like every per-pixel array
+__global__ void __launch_bounds__(256)
+hrt_motion_vectors_kernel(const hrt_float3* worldPos, ProjCam from, ProjCam cur, int width, int height,
+                          int rowBegin, int rowEnd, int stripN, int stripI, int nRows, hrt_float2* mv)
+{
+    long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (long long)nRows * width) return;
+    int lr = (int)(j / width), x = (int)(j % width);
+    int row = rowBegin + ((lr >> 3) * stripN + stripI) * 8 + (lr & 7);
+    if (row < rowEnd) motion_vector_pixel(worldPos, from, cur, width, height, mv, row * width + x);
 }
 
 __global__ void __launch_bounds__(256)
@@ -540,6 +564,11 @@ struct DeviceState {
     // presentation (TAAU history + display-size colour), device slot 0 only
     int32_t *present_color = nullptr, *taa_hist_color = nullptr, *taa_hist_obj = nullptr;
     int present_w = 0, present_h = 0; bool taa_history_valid = false;
+    // HRT_PRESENT_TAAU_REPROJECT: the pair a reprojecting resolve writes while it reads the current one (swapped after the launch;
+    // allocated by the first such present), and the camera of the frame last resolved into the history (valid with the history)
+    int32_t *taa_spare_color = nullptr, *taa_spare_obj = nullptr;
+    hrt_camera taa_hist_cam{};
+    float present_ms = 0.f;                    // HIP-event time of the last hrt_present's kernel (hrt_present_time)
     // streamed path-trace workspace
     // two sample batches are in flight at a time (lane 0 on stream / stream2, lane 1 on stream3 / stream4): each has its own workspace
     float* wf_mem[kMaxLanes] = {}; size_t wf_bytes[kMaxLanes] = {};
@@ -572,6 +601,8 @@ struct DeviceState {
     // rays, hit slots, counts and totals) and its pinned host staging; grown on demand, freed with the rest of the query state
     void* h_mem = nullptr; size_t h_bytes = 0;
     void* h_host = nullptr; size_t h_host_bytes = 0;
+    // hrt_motion_vectors, host path: the slot's vectors before they are gathered (8 B per pixel, global pixel index)
+    void* mv_mem = nullptr; size_t mv_bytes = 0;
 };
 
 } // namespace
@@ -598,6 +629,7 @@ struct hrt_ctx {
     int64_t n_positions = 0, n_spheres = 0;
     int64_t scene_count[15] = {};
     int width = 0, height = 0;
+    hrt_camera frame_cam{}, frame_prev_cam{};  // cam / prevCam of the last frame call (what gb_worldPos was rendered from)
     long long max_resident_paths = 0;          // hrt_set_workspace_limit: 0 = kWfMaxPaths
     std::vector<std::pair<char*, size_t>> pinned;   // hrt_host_register: page-locked ranges of the caller (gather targets)
     // the progressive frame a continuation (hrt_render_progressive with sample_begin > 0) may extend: what its last call rendered.
@@ -709,7 +741,10 @@ void free_present(DeviceState& d)
     if (d.present_color) (void)hipFree(d.present_color);
     if (d.taa_hist_color) (void)hipFree(d.taa_hist_color);
     if (d.taa_hist_obj) (void)hipFree(d.taa_hist_obj);
-    d.present_color = d.taa_hist_color = d.taa_hist_obj = nullptr; d.present_w = d.present_h = 0; d.taa_history_valid = false;
+    if (d.taa_spare_color) (void)hipFree(d.taa_spare_color);
+    if (d.taa_spare_obj) (void)hipFree(d.taa_spare_obj);
+    d.present_color = d.taa_hist_color = d.taa_hist_obj = d.taa_spare_color = d.taa_spare_obj = nullptr;
+    d.present_w = d.present_h = 0; d.taa_history_valid = false;
 }
 
 void free_workspace(DeviceState& d)
@@ -1612,6 +1647,8 @@ void free_query(DeviceState& d)
     if (d.h_mem) (void)hipFree(d.h_mem);
     if (d.h_host) (void)hipHostFree(d.h_host);
     d.h_mem = nullptr; d.h_host = nullptr; d.h_bytes = d.h_host_bytes = 0;
+    if (d.mv_mem) (void)hipFree(d.mv_mem);
+    d.mv_mem = nullptr; d.mv_bytes = 0;
 }
 
 // device staging for m rays (and the pinned host staging too when `host`); the caller has made d's device current
@@ -2947,6 +2984,7 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
         }
     }
     c->width = p->width; c->height = p->height;
+    c->frame_cam = p->cam; c->frame_prev_cam = p->prevCam;
 
     // 8-row strips of [rb,re) are dealt round-robin: this call owns strips s % sn == si, and
     // device i of the ctx takes every nd-th of those (sky rows are cheap, geometry rows are
@@ -3158,13 +3196,24 @@ try {
 }
 catch (...) { return on_exception(c, "hrt_render_progressive"); }
 
+// the camera as the reprojection kernels take it: tan(0.5 * fovY) evaluated once, here (hrt_tan is bit-equal on host and device)
+static ProjCam proj_cam(const hrt_camera& cam)
+{
+    ProjCam q;
+    q.origin = cam.origin; q.right = cam.right; q.up = cam.up; q.forward = cam.forward;
+    q.tanHalfFov = hrt_tan(0.5f * cam.fovYRadians); q.aspect = cam.aspect;
+    return q;
+}
+
 int hrt_present(hrt_ctx* c, const hrt_present_params* pp, int32_t* out_color_host)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
     if (!pp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: params is NULL");
     if (pp->out_width <= 0 || pp->out_height <= 0 || (int64_t)pp->out_width * pp->out_height > 0x7FFFFFFFLL)
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: output size must be positive");
-    if (pp->mode != HRT_PRESENT_RESAMPLE && pp->mode != HRT_PRESENT_TAAU) return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: unknown mode");
+    if (pp->mode != HRT_PRESENT_RESAMPLE && pp->mode != HRT_PRESENT_TAAU && pp->mode != HRT_PRESENT_TAAU_REPROJECT)
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: unknown mode");
+    const bool reproject = pp->mode == HRT_PRESENT_TAAU_REPROJECT;
     const int nd = (int)c->dev.size();
     DeviceState& d = c->dev[0];
     if (d.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, "hrt_present: no frame rendered yet");
@@ -3177,6 +3226,7 @@ try {
         DeviceState& srcd = c->dev[i];
         if ((rc = copy_strips(c, srcd, d.fb.color, (const int32_t*)srcd.fb.color, c->width, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
         if ((rc = copy_strips(c, srcd, d.fb.objectId, (const int32_t*)srcd.fb.objectId, c->width, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if (reproject && (rc = copy_strips(c, srcd, d.gb.worldPos, (const hrt_float3*)srcd.gb.worldPos, c->width, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
     }
     HIPCHK(c, hipSetDevice(d.device_id));
     const int outW = pp->out_width, outH = pp->out_height, inW = c->width, inH = c->height;
@@ -3190,7 +3240,9 @@ try {
         d.present_w = outW; d.present_h = outH; d.taa_history_valid = false;
     }
     const int blocks = (int)((outLen + 255) / 256);
-    if (pp->mode == HRT_PRESENT_TAAU)
+    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
+    HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
+    if (pp->mode == HRT_PRESENT_TAAU || reproject)
     {
         TaaK k;
         k.outColor = d.present_color; k.inColorLow = d.fb.color; k.inObjIdLow = d.fb.objectId;
@@ -3200,19 +3252,112 @@ try {
         k.sharpness = pp->sharpness <= 0.f ? 0.10f : pp->sharpness;        // header says: a NaN is not <= 0 and goes through to the kernel,
         k.clampK = pp->clampK <= 0.f ? 1.25f : pp->clampK;                 // as a NaN written to the reference's public fields would
         k.isFirstFrame = d.taa_history_valid ? 0 : 1;
-        hipLaunchKernelGGL(hrt_taa_resolve_kernel, dim3(std::min(blocks, 256 * 16)), dim3(256), 0, d.stream, k);
-        d.taa_history_valid = true;
+        if (!reproject)
+            hipLaunchKernelGGL(hrt_taa_resolve_kernel, dim3(std::min(blocks, 256 * 16)), dim3(256), 0, d.stream, k);
+        else
+        {   // reads the current history pair at reprojected positions, writes the spare pair at the pixel's own: swapped afterwards
+            if (!d.taa_spare_color) HIPCHK(c, dalloc(d.taa_spare_color, (int64_t)outLen, d.stream));
+            if (!d.taa_spare_obj) HIPCHK(c, dalloc(d.taa_spare_obj, (int64_t)outLen, d.stream));
+            TaaReprojK r;
+            r.worldPos = d.gb.worldPos; r.prevColor = d.taa_hist_color; r.prevObjId = d.taa_hist_obj;
+            k.historyColor = d.taa_spare_color; k.historyObjId = d.taa_spare_obj;
+            r.curCam = proj_cam(c->frame_cam);
+            r.histCam = proj_cam(d.taa_history_valid ? d.taa_hist_cam : c->frame_cam);      // no history: every pixel resets
+            hipLaunchKernelGGL(hrt_taa_resolve_reproject_kernel, dim3(std::min(blocks, 256 * 16)), dim3(256), 0, d.stream, k, r);
+            std::swap(d.taa_hist_color, d.taa_spare_color); std::swap(d.taa_hist_obj, d.taa_spare_obj);
+        }
+        d.taa_history_valid = true; d.taa_hist_cam = c->frame_cam;     // the camera the history now belongs to
     }
     else if (inW == outW && inH == outH)
         hipLaunchKernelGGL(hrt_blit_kernel, dim3(blocks), dim3(256), 0, d.stream, (const int32_t*)d.fb.color, (long long)d.nPix, d.present_color, (long long)outLen);
     else
         hipLaunchKernelGGL(hrt_bilinear_upsample_kernel, dim3(blocks), dim3(256), 0, d.stream, (const int32_t*)d.fb.color, inW, inH, d.present_color, outW, outH);
     HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
     if (out_color_host) HIPCHK(c, hipMemcpyAsync(out_color_host, d.present_color, outLen * 4, hipMemcpyDeviceToHost, d.stream));
     HIPCHK(c, hipStreamSynchronize(d.stream));
+    HIPCHK(c, hipEventElapsedTime(&d.present_ms, d.q_ev[0], d.q_ev[1]));
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_present"); }
+
+int hrt_present_time(hrt_ctx* c, float* ms)
+try {
+    if (!c || !ms) return HRT_ERR_INVALID_ARG;
+    *ms = c->dev[0].present_ms;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_present_time"); }
+
+int hrt_motion_vectors(hrt_ctx* c, const hrt_camera* from_cam, hrt_float2* mv, int32_t dev, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (!mv) return fail(c, HRT_ERR_INVALID_ARG, "hrt_motion_vectors: mv is NULL");
+    if (dev > 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_motion_vectors: dev must be 0 (device memory of slot 0) or negative (host memory)");
+    const int nd = (int)c->dev.size();
+    DeviceState& d0 = c->dev[0];
+    if (d0.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, "hrt_motion_vectors: no frame rendered yet");
+    if (d0.strip_n != nd || d0.row_begin != 0 || d0.row_end != c->height) return fail(c, HRT_ERR_INVALID_STATE, "hrt_motion_vectors: the last frame was a partial tile");
+    const int W = c->width, Hh = c->height;
+    const size_t bytes = (size_t)d0.nPix * sizeof(hrt_float2);
+    if (dev == 0)
+    {
+        HIPCHK(c, hipSetDevice(d0.device_id));
+        if (!on_device(d0, mv, bytes)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_motion_vectors: with dev == 0, mv must be device memory of slot 0's device, large enough for the frame");
+        if ((uintptr_t)mv & 7) return fail(c, HRT_ERR_INVALID_ARG, "hrt_motion_vectors: device mv must be 8-byte aligned");
+    }
+    else if (in_device_memory(mv)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_motion_vectors: with dev < 0, mv must be host memory (pass 0 for device memory of slot 0)");
+    int rc = hrt_synchronize(c, nullptr);
+    if (rc != HRT_OK) return rc;
+    const ProjCam from = proj_cam(from_cam ? *from_cam : c->frame_prev_cam), cur = proj_cam(c->frame_cam);
+    auto launch = [&](DeviceState& d, hrt_float2* out, int stripN, int stripI, int nRows) -> int {
+        if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
+        HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
+        const long long lanes = (long long)nRows * W;
+        if (lanes > 0)
+            hipLaunchKernelGGL(hrt_motion_vectors_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, d.stream,
+                               (const hrt_float3*)d.gb.worldPos, from, cur, W, Hh, 0, Hh, stripN, stripI, nRows, out);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
+        return HRT_OK;
+    };
+    auto elapsed = [&](DeviceState& d, float& best) -> int {
+        HIPCHK(c, hipSetDevice(d.device_id));
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        float t = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
+        best = std::max(best, t);
+        return HRT_OK;
+    };
+    float ms = 0.f;
+    if (dev == 0)
+    {   // everything on slot 0: bring the other slots' strips of gb_worldPos over, as hrt_present brings colour
+        for (int i = 1; i < nd; i++)
+            if ((rc = copy_strips(c, c->dev[(size_t)i], d0.gb.worldPos, (const hrt_float3*)c->dev[(size_t)i].gb.worldPos, W, hipMemcpyDeviceToDevice, d0.stream)) != HRT_OK) return rc;
+        if ((rc = launch(d0, mv, 1, 0, Hh)) != HRT_OK) return rc;
+        if ((rc = elapsed(d0, ms)) != HRT_OK) return rc;
+    }
+    else
+    {   // every slot computes the strips it rendered; gathered into the host array like a frame output
+        for (DeviceState& d : c->dev)
+        {
+            HIPCHK(c, hipSetDevice(d.device_id));
+            if (d.mv_bytes < bytes)
+            {
+                if (d.mv_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.mv_mem); d.mv_mem = nullptr; d.mv_bytes = 0; }
+                HIPCHK(c, hipMalloc(&d.mv_mem, bytes));
+                d.mv_bytes = bytes;
+            }
+            if ((rc = launch(d, (hrt_float2*)d.mv_mem, d.strip_n, d.strip_i, d.n_strips * 8)) != HRT_OK) return rc;      // a ragged last strip: the kernel's row test
+            if ((rc = gather_rows(c, d, mv, (const hrt_float2*)d.mv_mem, W)) != HRT_OK) return rc;
+        }
+        for (DeviceState& d : c->dev) if ((rc = elapsed(d, ms)) != HRT_OK) return rc;
+    }
+    if (device_ms) *device_ms = ms;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_motion_vectors"); }
 
 int hrt_set_workspace_limit(hrt_ctx* c, int64_t max_resident_paths)
 try {

@@ -59,6 +59,8 @@ def _load(path, hooks=False):
                                          C.POINTER(T.Stats)]
     L.hrt_synchronize.argtypes = [C.c_void_p, C.POINTER(T.Stats)]
     L.hrt_present.argtypes = [C.c_void_p, C.POINTER(T.PresentParams), C.c_void_p]
+    L.hrt_present_time.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.hrt_motion_vectors.argtypes = [C.c_void_p, C.POINTER(T.Camera), C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
     L.hrt_device_buffers.argtypes = [C.c_void_p, C.c_int, C.POINTER(T.DeviceViews)]
     L.hrt_reset_history.argtypes = [C.c_void_p]
     L.hrt_frame_times.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -362,6 +364,7 @@ class FrameHost:
         # private fields of the reference's RTRenderer (RTRenderer.cs:43-61), same defaults; `float` fields are numpy float32
         self.render_scale = np.float32(0.67)
         self.enable_taau = True
+        self.enable_reproject = False                             # not a field of the reference: TAAU with camera reprojection (render_direct)
         self.enable_temporal_reuse = 1
         self.enable_spatial_reuse = 1
         self.rng_lock_noise = 1
@@ -619,26 +622,60 @@ class RTRenderer(FrameHost):
         """Caps the streamed pipeline's path workspace (0 = default): larger frames run in sample batches, same results."""
         self._check(self._L.hrt_set_workspace_limit(self._ctx, int(max_resident_paths)))
 
-    def present(self, out_width, out_height, taau=True, out=None, feedback=0.0, sharpness=0.0, clamp_k=0.0):
+    def present(self, out_width, out_height, taau=True, out=None, feedback=0.0, sharpness=0.0, clamp_k=0.0, reproject=False):
         """Presentation step of RenderDirectToPbo (RTRenderer.cs:208-231): TAAU resolve, or blit / bilinear upsample.
-        Returns the display-size packed colour as an int32 array."""
-        pp = T.PresentParams(out_width, out_height, T.PRESENT_TAAU if taau else T.PRESENT_RESAMPLE, feedback, sharpness, clamp_k)
+        reproject (with taau): the history is read where the camera's motion since the last resolved frame puts it
+        (HRT_PRESENT_TAAU_REPROJECT, include/hip_raytrace.h).  Returns the display-size packed colour as an int32 array."""
+        if reproject and not taau:
+            raise ValueError("reproject is a mode of the TAAU resolve (taau=True)")
+        mode = T.PRESENT_TAAU_REPROJECT if reproject else (T.PRESENT_TAAU if taau else T.PRESENT_RESAMPLE)
+        pp = T.PresentParams(out_width, out_height, mode, feedback, sharpness, clamp_k)
         if out is None:
             out = np.zeros(out_width * out_height, np.int32)
         self._check(self._L.hrt_present(self._ctx, C.byref(pp), out.ctypes.data))
         return out
 
-    def render_direct(self, out_width, out_height, frame, dt=0.0, render_scale=None, taau=None, flags=0, outputs=None):
+    def present_ms(self):
+        """HIP-event time of the kernel of the last present() (hrt_present_time)."""
+        ms = C.c_float(0.0)
+        self._check(self._L.hrt_present_time(self._ctx, C.byref(ms)))
+        return ms.value
+
+    def render_direct(self, out_width, out_height, frame, dt=0.0, render_scale=None, taau=None, flags=0, outputs=None, reproject=None):
         """RenderDirectToPbo(pbo, width, height, frame, dt) end to end: internal size = round(out * renderScale) (RTRenderer.cs:109-116;
         render_scale / taau default to the fields render_scale = 0.67f / enable_taau), the two launches, then the presentation step.
-        outputs (optional, internal size) also receives the internal arrays.  Returns (display colour, Stats)."""
+        outputs (optional, internal size) also receives the internal arrays.  reproject (default: the field enable_reproject = False)
+        selects the reprojecting TAAU when TAAU is on.  Returns (display colour, Stats)."""
         out_w, out_h = max(1, out_width), max(1, out_height)
         in_w, in_h = self.internal_size(out_w, out_h, render_scale)
         p = self.make_params(in_w, in_h, frame, dt)
         st = self.render_params(p, outputs, flags)
-        out = self.present(out_w, out_h, self.enable_taau if taau is None else taau)
+        taau = self.enable_taau if taau is None else taau
+        out = self.present(out_w, out_h, taau, reproject=bool(taau and (self.enable_reproject if reproject is None else reproject)))
         self.end_frame()
         return out, st
+
+    def motion_vectors(self, from_cam=None, slot=None):
+        """Camera motion vectors of the last full-image frame (hrt_motion_vectors): for internal pixel i, where its surface point was
+        in the image of from_cam (a T.Camera; default: the frame's prevCam) minus where it is now, in pixels; NaN where the point is
+        behind either camera.  slot=None: host path over every device slot, returns an (height, width, 2) float32 numpy array.
+        slot=0: device path, returns a torch tensor of that shape on slot 0's device, no host copy."""
+        v = self.device_views(0)
+        w, h = v.width, v.height
+        cam = None if from_cam is None else C.byref(from_cam)
+        ms = C.c_float(0.0)
+        if slot is None:
+            out = np.zeros((h, w, 2), np.float32)
+            self._check(self._L.hrt_motion_vectors(self._ctx, cam, out.ctypes.data, -1, C.byref(ms)))
+        else:
+            if slot != 0:
+                raise ValueError("motion vectors stay on the device of slot 0 only (slot=0), or come to the host (slot=None)")
+            import torch                                       # lazy: the host path needs no torch
+            out = torch.zeros((h, w, 2), dtype=torch.float32, device="cuda:%d" % self.device_ids[0])
+            torch.cuda.synchronize(out.device)                 # the library works on its own streams
+            self._check(self._L.hrt_motion_vectors(self._ctx, cam, out.data_ptr(), 0, C.byref(ms)))
+        self.last_query_ms = ms.value
+        return out
 
     def reset_history(self):
         self._check(self._L.hrt_reset_history(self._ctx))

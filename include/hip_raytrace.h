@@ -25,6 +25,8 @@
  *                                                                Framebuffer.cs:148-160
  *   hrt_present            pbo.MapCuda + RTTaa.ResolveUpsample | BlitKernel | BilinearUpsampleKernel
  *                                                                RTRenderer.cs:208-231,281-345; RTTaa.cs:34-171
+ *                          HRT_PRESENT_TAAU_REPROJECT / hrt_motion_vectors: the reprojection the reference declares and
+ *                          leaves out                            RTTaa.cs:49-57,82-84; RTRay.cs:339-360
  *   hrt_synchronize        _cuda.Synchronize() when frames were enqueued without it  RTRenderer.cs:233
  *   hrt_device_buffers     GpuFramebuffer / GpuGBuffer views handed to the post kernels
  *                          (TAAU, blit) without leaving the device  RTRenderer.cs:155-161,208-231
@@ -166,9 +168,37 @@ typedef struct hrt_device_views {
 enum hrt_present_mode {
     HRT_PRESENT_RESAMPLE = 0,   /* _enableTAAU == false: BlitKernel when sizes match, else BilinearUpsampleKernel
                                    (RTRenderer.cs:225-231,281-345)                                              */
-    HRT_PRESENT_TAAU     = 1    /* RTTaa.ResolveUpsample (RTTaa.cs:49-171): history kept per display size,
+    HRT_PRESENT_TAAU     = 1,   /* RTTaa.ResolveUpsample (RTTaa.cs:49-171): history kept per display size,
                                    first frame after (re)allocation or hrt_reset_history ignores it             */
+    HRT_PRESENT_TAAU_REPROJECT = 2  /* the same resolve, with the history read where the camera's motion puts it (below) */
 };
+/* HRT_PRESENT_TAAU_REPROJECT finishes what the reference declares and ignores: ResolveUpsample(..., prevCam, curCam) never reads its
+ * cameras and motionScaleX / Y are 0 ("No motion vectors (engine-side)", RTTaa.cs:49-57,82-84,110-111).
+ * History camera: the context records, on slot 0, the cam of the frame a TAAU present (mode 1 or 2) last resolved into the history,
+ *   and reprojects from THAT camera, not from the caller's params.prevCam: the history stays right when the host skips a present,
+ *   presents twice or keeps prevCam for ReSTIR only.  The record goes wherever the history goes (hrt_reset_history, a new display
+ *   size, hrt_destroy).  hrt_render_progressive frames count as frames.
+ * Per output pixel idx = (px, py), float32 under the contract of hrt_math.h, statement order as written:
+ *   1. cur, nmin, nmax, the nearest low-res pixel (ix, iy) and objId as TaaResolveKernel computes them (RTTaa.cs:117-160).
+ *   2. P = gb_worldPos[iy * inW + ix] (a miss holds origin + dir * 1e6f: sky reprojects as a far point).
+ *   3. proj(C, P) = ReprojectToPrevPixel (RTRay.cs:339-355) with camera C for prevCam and outW, outH for width, height, stopped before
+ *      the (int) casts: p = P - C.origin; x, y, z = Dot(p, C.right / up / forward); ok = z > 1e-4f; t = hrt_tan(0.5f * C.fovYRadians);
+ *      fx = 0.5f * (x / (z * t * C.aspect) + 1f) * outW; fy = 0.5f * (y / (z * t) + 1f) * outH.
+ *   4. (okh, hx, hy) = proj(historyCam, P), (okc, cx, cy) = proj(cam of the frame, P); qx = (float)px + (hx - cx), qy = (float)py +
+ *      (hy - cy).  Both run the same expressions: a bitwise equal camera gives qx == px, qy == py exactly.  No snapping threshold.
+ *   5. valid = okh && okc && qx >= 0 && qx <= outW - 1 && qy >= 0 && qy <= outH - 1 (a NaN fails every comparison).
+ *   6. valid: x0 = floor(qx), fx = qx - x0, x1 = min(x0 + 1, outW - 1), likewise y; hist = (c00*(1-fx) + c10*fx)*(1-fy) +
+ *      (c01*(1-fx) + c11*fx)*fy over the four history texels unpacked with UnpackSRGB; histObj = historyObjId at the tap with the
+ *      larger weight (fx < 0.5f ? x0 : x1, same for y).  Not valid: the taps of (qx, qy) = (px, py); the value cannot reach the output.
+ *   7. reset = isFirstFrame || !valid || histObj != objId; from here on (clamp, blend, sharpen, PackSRGB) TaaResolveKernel unchanged.
+ *      The packed result goes to the output and to the history at idx, objId to historyObjId[idx].
+ * A lane reads history texels other lanes write, so slot 0 holds a second colour / objId pair (8 B per display pixel, allocated by
+ * the first mode-2 present) and swaps after each mode-2 resolve; mode 1 resolves in place on whichever pair is current, so modes 0, 1
+ * and 2 may alternate from frame to frame on one history.
+ * Static camera: with fx = fy = 0 step 6 returns c00 exactly, so where the history camera is bitwise the frame's, mode 2 writes what
+ * mode 1 writes, bit for bit, on every pixel whose P passes ok.
+ * Out of scope: object motion (instances moved by hrt_scene_update_* are handled as in mode 1, by the objId test and the clamp;
+ * every sphere carries objId -1, so there disocclusion rests on `valid` and the clamp), sub-pixel jitter, any depth plane in the history. */
 typedef struct hrt_present_params {
     int32_t out_width, out_height;
     int32_t mode;                              /* hrt_present_mode */
@@ -293,6 +323,21 @@ int  hrt_synchronize(hrt_ctx* ctx, hrt_stats* stats);
  * The last frame must have been a full-image render.  The resolve runs on device slot 0; a multi-device ctx first
  * brings the colour / objectId strips of its other devices there (device-to-device copies). */
 int  hrt_present(hrt_ctx* ctx, const hrt_present_params* params, int32_t* out_color_host);
+/* HIP-event time (ms) of the kernel of the last successful hrt_present (the resolve, blit or upsample alone: no strip or host
+ * copies); 0 before the first. */
+int  hrt_present_time(hrt_ctx* ctx, float* ms);
+
+/* The camera motion vectors of the last full-image frame, for hosts with a temporal filter of their own: mv[i] for internal pixel i =
+ * (hx - cx, hy - cy) of step 4 above with outW, outH = the frame's width, height, P = gb_worldPos[i] and from_cam as the history
+ * camera (NULL: the frame's params.prevCam), in pixels; (NaN, NaN) where okh && okc is false.  The same device function as the
+ * mode-2 resolve.
+ * dev < 0: mv is a host array of width * height; every device slot computes the strips it rendered, gathered as frame outputs are.
+ * dev == 0: mv is device memory of slot 0, 8-byte aligned (other slots' gb_worldPos strips are brought over first, as hrt_present
+ *   brings colour).  Any other dev, NULL mv, the wrong memory kind: HRT_ERR_INVALID_ARG.  No frame yet or a partial tile:
+ *   HRT_ERR_INVALID_STATE.
+ * Blocking.  device_ms (may be NULL): HIP-event time of the kernel (max over slots).  Frame state, present history and a pending
+ * progressive frame are untouched. */
+int  hrt_motion_vectors(hrt_ctx* ctx, const hrt_camera* from_cam, hrt_float2* mv, int32_t dev, float* device_ms);
 
 /* Per-frame HIP-event times (ms) of the frames the last hrt_synchronize (or blocking hrt_render_frame) collected on device
  * slot `dev`: launch 0 = primary visibility, 1 = the path-trace stage.  *n (may be NULL) receives their number; at most
