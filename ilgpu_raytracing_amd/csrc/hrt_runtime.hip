@@ -524,6 +524,14 @@ TreeletLimits g_treelet_limits;              // shipped values unless a test low
 constexpr int kMaxLanes = 4, kBatchLanes = HRT_BATCH_LANES;      // sample batches in flight: 1 / 2 / 3 / 4 measured on configs 4 / 5 at 64 / 256 spp: 362 / 328 / 334 / 325 ms and 1412 / 1323 / 1376 / 1330 ms
 static_assert(kBatchLanes >= 1 && kBatchLanes <= kMaxLanes, "");
 
+// Grow-only device (or pinned host) memory of one DeviceState.  It never shrinks and is reallocated only when it is too small.
+struct Scratch {
+    void* p = nullptr; size_t bytes = 0;
+    enum Drain { kStream, kDevice };           // what grow() waits for before it frees the old block (work enqueued earlier may use it)
+    int grow(hrt_ctx* c, size_t need, hipStream_t st, Drain drain = kStream, bool pinned = false);     // no-op when need <= bytes
+    void release(bool pinned = false);
+};
+
 struct DeviceState {
     int device_id = -1;
     int n_cu = 256;                            // compute units (MI355X: 256)
@@ -558,7 +566,7 @@ struct DeviceState {
     void* tlmem[3] = {};                       // reduced trees, treelet table, BLAS root -> reduced root
     DTreelets dtl{};
     bool tl_ok = false;                        // the treelets describe the BLASes as they are now (a vertex update or BLAS rebuild drops them)
-    void* tlq_mem[kMaxLanes] = {}; size_t tlq_bytes[kMaxLanes] = {};
+    Scratch tlq_mem[kMaxLanes];
     int max_lds = 65536;                       // LDS a workgroup may ask for
     bool blas_base_valid = false;              // saBase holds the node areas of the mesh BLASes as they were last built
     // presentation (TAAU history + display-size colour), device slot 0 only
@@ -571,13 +579,12 @@ struct DeviceState {
     float present_ms = 0.f;                    // HIP-event time of the last hrt_present's kernel (hrt_present_time)
     // streamed path-trace workspace
     // two sample batches are in flight at a time (lane 0 on stream / stream2, lane 1 on stream3 / stream4): each has its own workspace
-    float* wf_mem[kMaxLanes] = {}; size_t wf_bytes[kMaxLanes] = {};
-    int* wf_cnt[kMaxLanes] = {}; size_t wf_cnt_ints[kMaxLanes] = {};
-    float* wf_accum = nullptr; size_t wf_accum_floats = 0;     // Lframe carried across the batches of a frame (one plane set, shared)
+    Scratch wf_mem[kMaxLanes], wf_cnt[kMaxLanes];   // path state (float planes) and counters (ints) of a lane
+    Scratch wf_accum;                          // Lframe carried across the batches of a frame (one plane set of floats, shared)
     hipStream_t laneStream[kMaxLanes][2] = {};  // lanes >= 1: main and side stream (lane 0 uses stream / stream2)
     hipEvent_t evLane[kMaxLanes][3] = {};      // per lane: fork, join, resolve done
     hipEvent_t evStage = nullptr;
-    float* split_mem = nullptr; size_t split_floats = 0;    // fused kernel in sample groups: per-sample radiance + staged reservoirs
+    Scratch split_mem;                         // fused kernel in sample groups: per-sample radiance + staged reservoirs (floats)
     // per-pixel buffers, full image size on every device (rows outside the tile stay untouched)
     int64_t nPix = 0;
     DGBuffer gb{};
@@ -589,20 +596,14 @@ struct DeviceState {
     int row_begin = 0, row_end = 0;            // rows [row_begin,row_end) ...
     int strip_n = 1, strip_i = 0;              // ... of which this device owns 8-row strips s with s % strip_n == strip_i
     int n_strips = 0;
-    // ray queries (hrt_trace_rays): one chunk of rays in flight, allocated on the first query and grown on demand; separate from the
-    // frame's buffers, so hrt_device_views pointers never move because of a query
-    void* q_mem = nullptr; int64_t q_cap = 0;             // rays (32 B) + raw winners (16 B) + hits (48 B) per ray, then 8 hand-out counters
-    void* q_host = nullptr; int64_t q_host_cap = 0;       // pinned staging of the host path: rays + hits per ray
-    hipEvent_t q_ev[2] = {};
-    // radiance queries (hrt_trace_paths): rays and results are staged through q_mem / q_host; the chunk's G-buffer planes (48 B per slot)
-    // and the scratch planes of sample groups live here, never in the frame's buffers
-    void* p_mem = nullptr; size_t p_bytes = 0;
-    // multi-hit queries (hrt_trace_hits): private device workspace of one chunk (hand-out counters, and on the host path the staged
-    // rays, hit slots, counts and totals) and its pinned host staging; grown on demand, freed with the rest of the query state
-    void* h_mem = nullptr; size_t h_bytes = 0;
-    void* h_host = nullptr; size_t h_host_bytes = 0;
+    // caller-ray queries (hrt_trace_rays / hrt_trace_hits / hrt_trace_paths): one chunk in flight, shared by the three and carved per
+    // chunk by ChunkStager; grown on demand and separate from the frame's buffers, so hrt_device_views pointers never move because of a
+    // query and a radiance chunk's G-buffer and sample-group scratch never live in the frame's
+    Scratch q_dev;                             // the chunk's device workspace, then (host path) its staged caller arrays
+    Scratch q_pin;                             // pinned staging of the host path: the chunk's caller arrays
+    hipEvent_t q_ev[2] = {};                   // bracket the kernels of a chunk; hrt_present and hrt_motion_vectors time theirs with them too
     // hrt_motion_vectors, host path: the slot's vectors before they are gathered (8 B per pixel, global pixel index)
-    void* mv_mem = nullptr; size_t mv_bytes = 0;
+    Scratch mv_mem;
 };
 
 } // namespace
@@ -674,6 +675,46 @@ int on_exception(hrt_ctx* c, const char* who) noexcept
             return fail(ctx, e__ == hipErrorOutOfMemory ? HRT_ERR_OUT_OF_MEMORY : HRT_ERR_HIP,     \
                         std::string(#expr) + ": " + hipGetErrorString(e__));                       \
     } while (0)
+
+int Scratch::grow(hrt_ctx* c, size_t need, hipStream_t st, Drain drain, bool pinned)
+{
+    if (need <= bytes) return HRT_OK;
+    if (p) { HIPCHK(c, drain == kDevice ? hipDeviceSynchronize() : hipStreamSynchronize(st)); release(pinned); }
+    HIPCHK(c, pinned ? hipHostMalloc(&p, need, hipHostMallocPortable) : hipMalloc(&p, need));
+    bytes = need;
+    return HRT_OK;
+}
+
+void Scratch::release(bool pinned)
+{
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; bytes = 0;
+}
+
+// Runs fn(slot, ec) once per device slot: inline with ec = c, or, with `threads`, on one host thread per slot with ec = nullptr, so
+// that fn's error text lands in the worker's own g_create_error.  A call that blocks its issuing thread (a copy into pageable memory,
+// a synchronise) would otherwise serialise the slots.  Reports the first failing slot as "<who>: <what>device slot <i>: <text>".
+int for_each_slot(hrt_ctx* c, bool threads, const char* who, const char* what, const std::function<int(int, hrt_ctx*)>& fn)
+{
+    const int nd = (int)c->dev.size();
+    if (!threads)
+    {
+        for (int i = 0; i < nd; i++) { int rc = fn(i, c); if (rc != HRT_OK) return rc; }
+        return HRT_OK;
+    }
+    std::vector<int> rcs((size_t)nd, HRT_OK);
+    std::vector<std::string> errs((size_t)nd);
+    std::vector<std::thread> workers;
+    for (int i = 0; i < nd; i++)
+        workers.emplace_back([&, i]() {
+            try { rcs[(size_t)i] = fn(i, nullptr); if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error; }
+            catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
+        });
+    for (std::thread& t : workers) t.join();
+    for (int i = 0; i < nd; i++)
+        if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], std::string(who) + ": " + what + "device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
+    return HRT_OK;
+}
 
 void free_pixels(DeviceState& d)
 {
@@ -749,17 +790,9 @@ void free_present(DeviceState& d)
 
 void free_workspace(DeviceState& d)
 {
-    for (int j = 0; j < kMaxLanes; j++) { if (d.tlq_mem[j]) (void)hipFree(d.tlq_mem[j]); d.tlq_mem[j] = nullptr; d.tlq_bytes[j] = 0; }
-    for (int j = 0; j < kMaxLanes; j++)
-    {
-        if (d.wf_mem[j]) (void)hipFree(d.wf_mem[j]);
-        if (d.wf_cnt[j]) (void)hipFree(d.wf_cnt[j]);
-        d.wf_mem[j] = nullptr; d.wf_cnt[j] = nullptr; d.wf_bytes[j] = 0; d.wf_cnt_ints[j] = 0;
-    }
-    if (d.wf_accum) (void)hipFree(d.wf_accum);
-    d.wf_accum = nullptr; d.wf_accum_floats = 0;
-    if (d.split_mem) (void)hipFree(d.split_mem);
-    d.split_mem = nullptr; d.split_floats = 0;
+    for (int j = 0; j < kMaxLanes; j++) for (Scratch* s : {&d.tlq_mem[j], &d.wf_mem[j], &d.wf_cnt[j]}) s->release();
+    d.wf_accum.release();
+    d.split_mem.release();
 }
 
 void free_scene(DeviceState& d)
@@ -1265,50 +1298,28 @@ int ensure_workspace(hrt_ctx* c, DeviceState& d, int lane, long long cap, int nO
     const size_t planes = 2 * V_PLANES + R_PLANES + S_PLANES + 3 + G_PLANES;
     const size_t bytes = (size_t)planes * (size_t)cap * sizeof(float);
     const size_t ints = (size_t)(2 * maxDepth + 2) * (size_t)nRanges + (size_t)maxDepth * 16;
-    if (bytes > d.wf_bytes[lane])
-    {
-        if (d.wf_mem[lane]) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(d.wf_mem[lane]); d.wf_mem[lane] = nullptr; d.wf_bytes[lane] = 0; }
-        void* v = nullptr;
-        HIPCHK(c, hipMalloc(&v, bytes));
-        d.wf_mem[lane] = (float*)v; d.wf_bytes[lane] = bytes;
-    }
-    if (ints > d.wf_cnt_ints[lane])
-    {
-        if (d.wf_cnt[lane]) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(d.wf_cnt[lane]); d.wf_cnt[lane] = nullptr; d.wf_cnt_ints[lane] = 0; }
-        void* v = nullptr;
-        HIPCHK(c, hipMalloc(&v, ints * sizeof(int)));
-        d.wf_cnt[lane] = (int*)v; d.wf_cnt_ints[lane] = ints;
-    }
-    if ((size_t)3 * (size_t)nOrd > d.wf_accum_floats)
-    {
-        if (d.wf_accum) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(d.wf_accum); d.wf_accum = nullptr; d.wf_accum_floats = 0; }
-        void* v = nullptr;
-        HIPCHK(c, hipMalloc(&v, (size_t)3 * (size_t)nOrd * sizeof(float)));
-        d.wf_accum = (float*)v; d.wf_accum_floats = (size_t)3 * (size_t)nOrd;
-    }
+    int rc;
+    if ((rc = d.wf_mem[lane].grow(c, bytes, d.stream, Scratch::kDevice)) != HRT_OK) return rc;
+    if ((rc = d.wf_cnt[lane].grow(c, ints * sizeof(int), d.stream, Scratch::kDevice)) != HRT_OK) return rc;
+    if ((rc = d.wf_accum.grow(c, (size_t)3 * (size_t)nOrd * sizeof(float), d.stream, Scratch::kDevice)) != HRT_OK) return rc;
     if (d.tl_ok && treelets)
     {   // queues of the treelet walker (only for frames that ask for it: HRT_FLAG_TREELETS): per walk kind key / state / binned indices over the path slots, and the per-treelet counters
         const size_t nTl = (size_t)d.dtl.nTl;
         const size_t ints = ((nTl + 32 + nTl + 1 + nTl) + 63) & ~(size_t)63;
         const size_t per0 = (size_t)cap * (4 + 16 + 4) + ints * 4, per1 = (size_t)cap * (4 + 32 + 4) + ints * 4;
         const size_t need = ((per0 + 255) & ~(size_t)255) + per1;
-        if (need > d.tlq_bytes[lane])
-        {
-            if (d.tlq_mem[lane]) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(d.tlq_mem[lane]); d.tlq_mem[lane] = nullptr; d.tlq_bytes[lane] = 0; }
-            void* v = nullptr;
-            HIPCHK(c, hipMalloc(&v, need));
-            d.tlq_mem[lane] = v; d.tlq_bytes[lane] = need;
-        }
+        if ((rc = d.tlq_mem[lane].grow(c, need, d.stream, Scratch::kDevice)) != HRT_OK) return rc;
     }
-    float* m = d.wf_mem[lane];
+    float* m = (float*)d.wf_mem[lane].p;
+    int* cnt = (int*)d.wf_cnt[lane].p;
     auto take = [&](int nplanes, long long stride) { Planes pl; pl.base = m; pl.stride = stride; m += (size_t)nplanes * (size_t)stride; return pl; };
     W.A = take(V_PLANES, cap); W.B = take(V_PLANES, cap); W.R = take(R_PLANES, cap); W.SQ = take(S_PLANES, cap);
     static_assert(V_POS == 0 && V_LI >= R_PLANES && V_PID >= R_PLANES && R_PLANES >= S_PLANES, "the second request set aliases the vertex planes below V_LI");
     W.Rn = W.A; W.SQn = W.B; W.pingpong = 0;
     W.sampleLi = take(3, cap); W.stage = take(G_PLANES, cap);
-    W.accum.base = d.wf_accum; W.accum.stride = nOrd;
-    W.cntA = d.wf_cnt[lane]; W.cntS = d.wf_cnt[lane] + (size_t)(maxDepth + 1) * (size_t)nRanges;
-    W.grab = d.wf_cnt[lane] + (size_t)(2 * maxDepth + 2) * (size_t)nRanges;
+    W.accum.base = (float*)d.wf_accum.p; W.accum.stride = nOrd;
+    W.cntA = cnt; W.cntS = cnt + (size_t)(maxDepth + 1) * (size_t)nRanges;
+    W.grab = cnt + (size_t)(2 * maxDepth + 2) * (size_t)nRanges;
     W.nRanges = nRanges;
     return HRT_OK;
 }
@@ -1320,7 +1331,7 @@ TlQueues tl_queues(const DeviceState& d, int lane, int kind, long long cap)
     const size_t nTl = (size_t)d.dtl.nTl;
     const size_t ints = ((nTl + 32 + nTl + 1 + nTl) + 63) & ~(size_t)63;
     const size_t per0 = (size_t)cap * (4 + 16 + 4) + ints * 4;
-    char* p = (char*)d.tlq_mem[lane] + (kind ? ((per0 + 255) & ~(size_t)255) : 0);
+    char* p = (char*)d.tlq_mem[lane].p + (kind ? ((per0 + 255) & ~(size_t)255) : 0);
     TlQueues Q;
     Q.state = (float4*)p; p += (size_t)cap * (kind ? 32 : 16);
     Q.key = (int*)p; p += (size_t)cap * 4;
@@ -1356,6 +1367,26 @@ int launch_tl_walk(hrt_ctx* c, DeviceState& d, const TracerPackedT<F>& tr, const
     return HRT_OK;
 }
 
+// Sample groups of the fused path stage: when a launch of `waves` waves gives the machine less than ~5 rounds of them, the sppCall
+// samples it renders are spread over nGroups workgroups per tile, perGroup samples each; the per-sample radiance of all sppAll samples
+// of the frame and the groups' staged reservoirs then go through scratchFloats floats per lane of the launch.  One group: no scratch.
+// A frame (run_path_stage) and a radiance query (paths_slot) both ask here, which is what keeps them bit-equal on camera rays.
+struct SampleGroups { int nGroups, perGroup; size_t scratchFloats; };
+SampleGroups sample_groups(int sppCall, int sppAll, int maxDepth, long long waves, int n_cu)
+{
+    const long long slots = (long long)n_cu * 4 * HRT_PT_WAVES;
+    SampleGroups g{1, sppCall, 0};
+    if (maxDepth <= 64 && sppCall > 1 && waves < 5 * slots)
+        g.nGroups = (int)std::min<long long>(std::min(sppCall, 8), (16 * slots + waves - 1) / waves);   // config 2 over N = 2 / 4 / 8 ranks: 4 groups each (1.111 -> 1.079, 0.593 -> 0.555, 0.296 ms)
+    if (g.nGroups > 1)
+    {
+        g.perGroup = (sppCall + g.nGroups - 1) / g.nGroups;
+        g.nGroups = (sppCall + g.perGroup - 1) / g.perGroup;
+        g.scratchFloats = (size_t)sppAll * 3 + (size_t)g.nGroups * 12;
+    }
+    return g;
+}
+
 template <class TR> struct PackedFeat { static constexpr int value = -1; };
 template <int F> struct PackedFeat<TracerPackedT<F>> { static constexpr int value = F; };
 
@@ -1378,26 +1409,17 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
         // sample groups when the tile gives the machine less than ~5 rounds of waves
         const int sppAll = k.spp > 1 ? k.spp : 1;
         const int sppN = sppAll - sBegin;                            // samples of this call
-        const long long waves = (long long)tm.nTiles * tm.wpb, slots = (long long)d.n_cu * 4 * HRT_PT_WAVES;
-        int nGroups = 1;
-        if (!count && k.maxDepth <= 64 && sppN > 1 && waves > 0 && waves < 5 * slots)
-            nGroups = (int)std::min<long long>(std::min(sppN, 8), (16 * slots + waves - 1) / waves);   // config 2 over N = 2 / 4 / 8 ranks: 4 groups each (1.111 -> 1.079, 0.593 -> 0.555, 0.296 ms)
+        const long long waves = (long long)tm.nTiles * tm.wpb;
+        const SampleGroups sg = !count && waves > 0 ? sample_groups(sppN, sppAll, k.maxDepth, waves, d.n_cu) : SampleGroups{1, sppN, 0};
+        const int nGroups = sg.nGroups, perGroup = sg.perGroup;
         if (nGroups > 1)
         {
-            const int perGroup = (sppN + nGroups - 1) / nGroups;
-            nGroups = (sppN + perGroup - 1) / perGroup;
             // scratch planes over the lanes of THIS launch's tiles (a rank's share of the frame), not over the image
             const size_t nLocal = (size_t)tm.nTiles * 64 * (size_t)tm.wpb;
-            const size_t need = ((size_t)sppAll * 3 + (size_t)nGroups * 12) * nLocal;
-            if (need > d.split_floats)
-            {
-                if (d.split_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.split_mem); d.split_mem = nullptr; d.split_floats = 0; }
-                void* v = nullptr;
-                HIPCHK(c, hipMalloc(&v, need * sizeof(float)));
-                d.split_mem = (float*)v; d.split_floats = need;
-            }
-            hrt_float3* li = (hrt_float3*)d.split_mem;
-            float* stage = d.split_mem + (size_t)sppAll * 3 * nLocal;
+            int rc = d.split_mem.grow(c, sg.scratchFloats * nLocal * sizeof(float), d.stream);
+            if (rc != HRT_OK) return rc;
+            hrt_float3* li = (hrt_float3*)d.split_mem.p;
+            float* stage = (float*)d.split_mem.p + (size_t)sppAll * 3 * nLocal;
             if (prog)
             {
                 if (noReuse) { if constexpr (std::is_same<TR, TracerFlat>::value) hipLaunchKernelGGL((hrt_path_trace_split_prog_kernel<TR, false>), dim3(tm.nTiles * nGroups), block, 0, d.stream, tr, k, d.gb, d.fb, resPrev, resCur, nPix, tm, li, stage, nGroups, perGroup, sBegin); }
@@ -1634,41 +1656,86 @@ int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, 
 // holds is bounded for any n; a 1920x1080 set of rays is one chunk.
 // ---------------------------------------------------------------------------------------
 constexpr int64_t kQueryChunk = HRT_QUERY_CHUNK;
-constexpr size_t kQueryDevBytes = 32 + 16 + 48, kQueryHostBytes = 32 + 48;
+constexpr size_t kQueryGrabBytes = 8 * kQueryGrabStride * sizeof(int);      // the hand-out counters of a packed walk
+constexpr int kMaxQueryArgs = 4;
+
+// One caller array of a query: `stride` bytes per ray; device pointers must be `align`-byte aligned (16 where the kernels read or write
+// float4, 4 for ints), and the staged copy starts so.  args[0] holds the rays (read), the others are results (written); only an
+// optional one (totals) may be null.
+struct QueryArg { const void* p; size_t stride; unsigned align; bool optional; };
 
 void free_query(DeviceState& d)
 {
-    if (d.q_mem) (void)hipFree(d.q_mem);
-    if (d.q_host) (void)hipHostFree(d.q_host);
+    d.q_dev.release();
+    d.q_pin.release(true);
+    d.mv_mem.release();
     for (hipEvent_t& e : d.q_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    d.q_mem = nullptr; d.q_host = nullptr; d.q_cap = d.q_host_cap = 0;
-    if (d.p_mem) (void)hipFree(d.p_mem);
-    d.p_mem = nullptr; d.p_bytes = 0;
-    if (d.h_mem) (void)hipFree(d.h_mem);
-    if (d.h_host) (void)hipHostFree(d.h_host);
-    d.h_mem = nullptr; d.h_host = nullptr; d.h_bytes = d.h_host_bytes = 0;
-    if (d.mv_mem) (void)hipFree(d.mv_mem);
-    d.mv_mem = nullptr; d.mv_bytes = 0;
 }
 
-// device staging for m rays (and the pinned host staging too when `host`); the caller has made d's device current
-int ensure_query(hrt_ctx* c, DeviceState& d, int64_t m, bool host)
+// p .. p + bytes lies in a range the caller page-locked (hrt_host_register): copies go straight to it, without pinned staging
+bool registered(const hrt_ctx& cc, const void* p, size_t bytes)
 {
-    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
-    if (d.q_cap < m)
-    {
-        if (d.q_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.q_mem); d.q_mem = nullptr; d.q_cap = 0; }
-        HIPCHK(c, hipMalloc(&d.q_mem, (size_t)m * kQueryDevBytes + 8 * kQueryGrabStride * sizeof(int)));
-        d.q_cap = m;
-    }
-    if (host && d.q_host_cap < m)
-    {
-        if (d.q_host) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipHostFree(d.q_host); d.q_host = nullptr; d.q_host_cap = 0; }
-        HIPCHK(c, hipHostMalloc(&d.q_host, (size_t)m * kQueryHostBytes, hipHostMallocPortable));
-        d.q_host_cap = m;
-    }
-    return HRT_OK;
+    for (const auto& r : cc.pinned) if ((const char*)p >= r.first && (const char*)p + bytes <= r.first + r.second) return true;
+    return false;
 }
+
+// The chunk sequence of a query on slot d's main stream (after any frame in flight), for rays [off, off + m) of the caller's arrays:
+//   begin(): device workspace of workBytes (`work`) and the device addresses of the chunk's arrays (`dev`); H2D of the rays, first event
+//   (the slot function enqueues its kernels)
+//   end():   second event, one D2H per result array, synchronise, *ms += the events' time -- the kernels only
+// dev_ptrs: the arrays are device memory of this slot: `dev` are the caller's own pointers, nothing is staged or allocated beyond `work`.
+// Otherwise the arrays are carved behind the workspace in q_dev and, unless the caller registered their range, pass through q_pin.
+// Both buffers grow only for a chunk that needs more than any before it.  The caller has made d's device current.
+struct ChunkStager {
+    hrt_ctx* c; const hrt_ctx& cc; DeviceState& d; const QueryArg* args; int nArgs; bool dev_ptrs;
+    void* work = nullptr;
+    void* dev[kMaxQueryArgs] = {};
+    char* user[kMaxQueryArgs] = {}; char* pin[kMaxQueryArgs] = {}; size_t bytes[kMaxQueryArgs] = {};     // pin[i] == nullptr: no staging
+
+    int begin(int64_t off, int64_t m, size_t workBytes)
+    {
+        size_t devNeed = (workBytes + 15) & ~(size_t)15, pinNeed = 0, devOff[kMaxQueryArgs] = {}, pinOff[kMaxQueryArgs] = {};
+        for (int i = 0; i < nArgs; i++)
+        {
+            user[i] = args[i].p ? (char*)args[i].p + (size_t)off * args[i].stride : nullptr;
+            bytes[i] = user[i] ? (size_t)m * args[i].stride : 0;
+            if (dev_ptrs) continue;
+            const size_t a = args[i].align - 1;
+            devOff[i] = devNeed = (devNeed + a) & ~a; devNeed += bytes[i];
+            pinOff[i] = pinNeed = (pinNeed + a) & ~a; pinNeed += bytes[i];
+        }
+        int rc;
+        if ((rc = d.q_dev.grow(c, devNeed, d.stream)) != HRT_OK) return rc;
+        if ((rc = d.q_pin.grow(c, pinNeed, d.stream, Scratch::kStream, true)) != HRT_OK) return rc;
+        work = d.q_dev.p;
+        for (int i = 0; i < nArgs; i++)
+        {
+            dev[i] = dev_ptrs || !user[i] ? (void*)user[i] : (void*)((char*)d.q_dev.p + devOff[i]);
+            pin[i] = dev_ptrs || !user[i] || registered(cc, user[i], bytes[i]) ? nullptr : (char*)d.q_pin.p + pinOff[i];
+        }
+        if (!dev_ptrs)
+        {
+            if (pin[0]) std::memcpy(pin[0], user[0], bytes[0]);
+            HIPCHK(c, hipMemcpyAsync(dev[0], pin[0] ? pin[0] : user[0], bytes[0], hipMemcpyHostToDevice, d.stream));
+        }
+        HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
+        return HRT_OK;
+    }
+
+    int end(float* ms)
+    {
+        HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
+        if (!dev_ptrs)
+            for (int i = 1; i < nArgs; i++)
+                if (user[i]) HIPCHK(c, hipMemcpyAsync(pin[i] ? pin[i] : user[i], dev[i], bytes[i], hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        float t = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
+        *ms += t;
+        for (int i = 1; i < nArgs; i++) if (pin[i]) std::memcpy(user[i], pin[i], bytes[i]);
+        return HRT_OK;
+    }
+};
 
 template <int F>
 void launch_query_packed(const DeviceState& d, int query, const QueryK& q, hipStream_t st)
@@ -1702,7 +1769,7 @@ int launch_query(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const
 {
     if (cc.packed_ok)
     {
-        HIPCHK(c, hipMemsetAsync(q.grab, 0, 8 * kQueryGrabStride * sizeof(int), st));
+        HIPCHK(c, hipMemsetAsync(q.grab, 0, kQueryGrabBytes, st));
         if (cc.packed_feat == 0)      launch_query_packed<0>(d, query, q, st);
         else if (cc.packed_feat == 1) launch_query_packed<1>(d, query, q, st);
         else                          launch_query_packed<3>(d, query, q, st);
@@ -1719,56 +1786,25 @@ int launch_query(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const
     return HRT_OK;
 }
 
-// rays [begin, end) of one device slot, chunk by chunk: H2D, walk, finish, D2H on the slot's main stream (after any frame in flight).
-// dev_ptrs: rays / results are device memory of this slot.  *ms += the HIP-event time of the kernels.
-int query_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const hrt_ray* rays, void* results, int64_t begin, int64_t end,
-               bool dev_ptrs, float* ms)
+// rays [begin, end) of one device slot, chunk by chunk (ChunkStager): walk, finish, fix-up.  The chunk's workspace is the raw winners of
+// the walk (16 B per ray), then the 8 hand-out counters.
+int query_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const QueryArg* args, int64_t begin, int64_t end, bool dev_ptrs, float* ms)
 {
     HIPCHK(c, hipSetDevice(d.device_id));
-    const size_t resBytes = query == HRT_QUERY_CLOSEST ? sizeof(hrt_ray_hit) : sizeof(int32_t);
-    auto registered = [&](const void* p, size_t bytes) {
-        for (const auto& r : cc.pinned) if ((const char*)p >= r.first && (const char*)p + bytes <= r.first + r.second) return true;
-        return false;
-    };
-    const hipStream_t st = d.stream;
+    ChunkStager s{c, cc, d, args, 2, dev_ptrs};
     for (int64_t off = begin; off < end; off += kQueryChunk)
     {
         const int64_t m = std::min<int64_t>(kQueryChunk, end - off);
-        int rc = ensure_query(c, d, m, !dev_ptrs);
+        int rc = s.begin(off, m, (size_t)m * 16 + kQueryGrabBytes);
         if (rc != HRT_OK) return rc;
-        char* base = (char*)d.q_mem;
         QueryK q;
-        q.raw = (float4*)(base + (size_t)d.q_cap * 32);
-        q.grab = (int*)(base + (size_t)d.q_cap * kQueryDevBytes);
+        q.raw = (float4*)s.work;
+        q.grab = (int*)((char*)s.work + (size_t)m * 16);
         q.n = (int)m; q.nSegs = (int)((m + kQuerySeg - 1) / kQuerySeg);
-        const hrt_ray* src = rays + off;
-        char* dst = (char*)results + (size_t)off * resBytes;
-        const bool rayReg = !dev_ptrs && registered(src, (size_t)m * sizeof(hrt_ray));
-        const bool resReg = !dev_ptrs && registered(dst, (size_t)m * resBytes);
-        char* hostRays = (char*)d.q_host;
-        char* hostRes = (char*)d.q_host + (size_t)d.q_host_cap * 32;
-        if (dev_ptrs)
-        {
-            q.rays = (const float4*)src;
-            q.hits = (float4*)dst; q.occ = (int32_t*)dst;
-        }
-        else
-        {
-            q.rays = (const float4*)base;
-            q.hits = (float4*)(base + (size_t)d.q_cap * 48); q.occ = (int32_t*)q.hits;
-            if (!rayReg) std::memcpy(hostRays, src, (size_t)m * sizeof(hrt_ray));
-            HIPCHK(c, hipMemcpyAsync(base, rayReg ? (const void*)src : (const void*)hostRays, (size_t)m * sizeof(hrt_ray), hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
-        rc = launch_query(c, cc, d, query, q, st);
-        if (rc != HRT_OK) return rc;
-        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
-        if (!dev_ptrs) HIPCHK(c, hipMemcpyAsync(resReg ? (void*)dst : (void*)hostRes, q.hits, (size_t)m * resBytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
-        *ms += t;
-        if (!dev_ptrs && !resReg) std::memcpy(dst, hostRes, (size_t)m * resBytes);
+        q.rays = (const float4*)s.dev[0];
+        q.hits = (float4*)s.dev[1]; q.occ = (int32_t*)s.dev[1];
+        if ((rc = launch_query(c, cc, d, query, q, d.stream)) != HRT_OK) return rc;
+        if ((rc = s.end(ms)) != HRT_OK) return rc;
     }
     return HRT_OK;
 }
@@ -1776,98 +1812,30 @@ int query_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int query, const h
 // ---------------------------------------------------------------------------------------
 // Multi-hit queries (hrt_trace_hits, kernels in hrt_hits.hip).  A chunk holds at most kQueryChunk hit slots (rays * k), so the staging
 // does not grow with k.  The walk keeps each ray's candidates in the ray's own hit slots and the finish shades them in place: the
-// device workspace is the 8 hand-out counters, plus the staged rays, hit slots, counts and totals on the host path.
+// device workspace is the 8 hand-out counters.
 // ---------------------------------------------------------------------------------------
-constexpr size_t kHitsGrabBytes = 8 * kQueryGrabStride * sizeof(int);
-
-int ensure_hits(hrt_ctx* c, DeviceState& d, size_t devBytes, size_t hostBytes)
-{
-    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
-    if (d.h_bytes < devBytes)
-    {
-        if (d.h_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.h_mem); d.h_mem = nullptr; d.h_bytes = 0; }
-        HIPCHK(c, hipMalloc(&d.h_mem, devBytes));
-        d.h_bytes = devBytes;
-    }
-    if (hostBytes && d.h_host_bytes < hostBytes)
-    {
-        if (d.h_host) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipHostFree(d.h_host); d.h_host = nullptr; d.h_host_bytes = 0; }
-        HIPCHK(c, hipHostMalloc(&d.h_host, hostBytes, hipHostMallocPortable));
-        d.h_host_bytes = hostBytes;
-    }
-    return HRT_OK;
-}
-
-// rays [begin, end) of one device slot, chunk by chunk on the slot's main stream (after any frame in flight): H2D of the rays, walk,
-// finish, fix-up, D2H of hits, counts and totals.  dev_ptrs: the arrays are device memory of this slot.  *ms += kernel time.
-int hits_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_ray* rays, int k, hrt_ray_hit* hits,
-              int32_t* counts, int32_t* totals, int64_t begin, int64_t end, bool dev_ptrs, float* ms)
+// rays [begin, end) of one device slot, chunk by chunk (ChunkStager): walk, finish, fix-up
+int hits_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, int k, const QueryArg* args, int64_t begin, int64_t end, bool dev_ptrs, float* ms)
 {
     HIPCHK(c, hipSetDevice(d.device_id));
-    auto registered = [&](const void* p, size_t bytes) {
-        for (const auto& r : cc.pinned) if ((const char*)p >= r.first && (const char*)p + bytes <= r.first + r.second) return true;
-        return false;
-    };
-    const hipStream_t st = d.stream;
+    ChunkStager s{c, cc, d, args, 4, dev_ptrs};
     const int64_t per = std::max<int64_t>(1, kQueryChunk / k);          // rays per chunk: at most kQueryChunk hit slots
-    const int64_t cap = std::min<int64_t>(per, end - begin);
-    const size_t raysB = (size_t)cap * sizeof(hrt_ray), hitsB = (size_t)cap * k * sizeof(hrt_ray_hit), intsB = (size_t)cap * sizeof(int32_t);
-    int rc = ensure_hits(c, d, kHitsGrabBytes + (dev_ptrs ? 0 : raysB + hitsB + 2 * intsB), dev_ptrs ? 0 : raysB + hitsB + 2 * intsB);
-    if (rc != HRT_OK) return rc;
-    char* dbase = (char*)d.h_mem;
-    char* hbase = (char*)d.h_host;
     for (int64_t off = begin; off < end; off += per)
     {
         const int64_t m = std::min<int64_t>(per, end - off);
+        int rc = s.begin(off, m, kQueryGrabBytes);
+        if (rc != HRT_OK) return rc;
         HitsLaunch L;
         L.variant = cc.packed_ok ? cc.packed_feat : -1;
         L.lt3 = cc.packed_feat != 0 && d.dpacked.leafTris == 3;
         L.S = d.dscene; L.P = d.dpacked;
         HitsK& h = L.h;
-        h.grab = (int*)dbase;
+        h.grab = (int*)s.work;
         h.n = (int)m; h.k = k; h.nSegs = (int)((m + kQuerySeg - 1) / kQuerySeg);
         L.gridW = (unsigned)std::min<long long>((h.nSegs + 3) / 4, (long long)d.n_cu * kWalkBlocksPerCU);     // persistent waves, as hrt_trace_rays
-        const hrt_ray* src = rays + off;
-        hrt_ray_hit* dHits = hits + (size_t)off * k;
-        int32_t* dCounts = counts + off;
-        int32_t* dTotals = totals ? totals + off : nullptr;
-        const size_t mRays = (size_t)m * sizeof(hrt_ray), mHits = (size_t)m * k * sizeof(hrt_ray_hit), mInts = (size_t)m * sizeof(int32_t);
-        const bool rayReg = !dev_ptrs && registered(src, mRays);
-        const bool hitReg = !dev_ptrs && registered(dHits, mHits);
-        const bool cntReg = !dev_ptrs && registered(dCounts, mInts);
-        const bool totReg = !dev_ptrs && dTotals && registered(dTotals, mInts);
-        char* sRays = hbase; char* sHits = hbase + raysB; char* sCounts = sHits + hitsB; char* sTotals = sCounts + intsB;
-        if (dev_ptrs)
-        {
-            h.rays = (const float4*)src; h.hits = (float4*)dHits; h.counts = dCounts; h.totals = dTotals;
-        }
-        else
-        {
-            char* p = dbase + kHitsGrabBytes;
-            h.rays = (const float4*)p; h.hits = (float4*)(p + raysB); h.counts = (int32_t*)(p + raysB + hitsB);
-            h.totals = dTotals ? (int32_t*)(p + raysB + hitsB + intsB) : nullptr;
-            if (!rayReg) std::memcpy(sRays, src, mRays);
-            HIPCHK(c, hipMemcpyAsync((void*)h.rays, rayReg ? (const void*)src : (const void*)sRays, mRays, hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
-        HIPCHK(c, hits_launch(L, st));
-        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
-        if (!dev_ptrs)
-        {
-            HIPCHK(c, hipMemcpyAsync(hitReg ? (void*)dHits : (void*)sHits, h.hits, mHits, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipMemcpyAsync(cntReg ? (void*)dCounts : (void*)sCounts, h.counts, mInts, hipMemcpyDeviceToHost, st));
-            if (dTotals) HIPCHK(c, hipMemcpyAsync(totReg ? (void*)dTotals : (void*)sTotals, h.totals, mInts, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(c, hipStreamSynchronize(st));
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
-        *ms += t;
-        if (!dev_ptrs)
-        {
-            if (!hitReg) std::memcpy(dHits, sHits, mHits);
-            if (!cntReg) std::memcpy(dCounts, sCounts, mInts);
-            if (dTotals && !totReg) std::memcpy(dTotals, sTotals, mInts);
-        }
+        h.rays = (const float4*)s.dev[0]; h.hits = (float4*)s.dev[1]; h.counts = (int32_t*)s.dev[2]; h.totals = (int32_t*)s.dev[3];
+        HIPCHK(c, hits_launch(L, d.stream));
+        if ((rc = s.end(ms)) != HRT_OK) return rc;
     }
     return HRT_OK;
 }
@@ -1889,6 +1857,51 @@ bool on_device(const DeviceState& d, const void* p, size_t bytes)
     hipDeviceptr_t lo = nullptr; size_t size = 0;
     if (hipMemGetAddressRange(&lo, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return (const char*)p >= (const char*)lo && (const char*)p + bytes <= (const char*)lo + size;
+}
+
+// What the three caller-ray queries share once an entry point has made its own checks.  The texts carry the function's words:
+// `needed` the arrays a call with n > 0 must pass, `all` every array, `aligned` the alignment rule of device pointers.
+struct QueryDoor { const char* who; const char* needed; const char* all; const char* aligned; bool sceneBeforeEmpty; };
+using QuerySlotFn = std::function<int(hrt_ctx* ec, DeviceState& d, int64_t begin, int64_t end, bool dev_ptrs, float* ms)>;
+
+// dev >= 0: the arrays are device memory of that slot, walked in place.  dev < 0: host memory, cut into one contiguous part per
+// device slot; *device_ms is the largest of the slots' kernel times.
+int run_query(hrt_ctx* c, const QueryDoor& q, const QueryArg* args, int nArgs, int64_t n, int32_t dev, float* device_ms, const QuerySlotFn& slot)
+{
+    const std::string who = std::string(q.who) + ": ";
+    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, who + "n must be >= 0");
+    for (int i = 0; i < nArgs; i++)
+        if (n > 0 && !args[i].p && !args[i].optional) return fail(c, HRT_ERR_INVALID_ARG, who + q.needed + " are needed when n > 0");
+    const int nd = (int)c->dev.size();
+    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, who + "device slot out of range");
+    if (n == 0 && !q.sceneBeforeEmpty) return HRT_OK;
+    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, who + "no scene uploaded (call hrt_scene_upload first)");
+    if (n == 0) return HRT_OK;
+    if (dev >= 0)
+    {
+        DeviceState& d = c->dev[(size_t)dev];
+        HIPCHK(c, hipSetDevice(d.device_id));
+        for (int i = 0; i < nArgs; i++)
+            if (args[i].p && !on_device(d, args[i].p, (size_t)n * args[i].stride))
+                return fail(c, HRT_ERR_INVALID_ARG, who + "with dev >= 0, " + q.all + " must be device memory of that slot's device, large enough for n");
+        for (int i = 0; i < nArgs; i++)
+            if ((uintptr_t)args[i].p & (args[i].align - 1)) return fail(c, HRT_ERR_INVALID_ARG, who + "device " + q.aligned);
+        float ms = 0.f;
+        int rc = slot(c, d, 0, n, true, &ms);
+        if (rc != HRT_OK) return rc;
+        if (device_ms) *device_ms = ms;
+        return HRT_OK;
+    }
+    for (int i = 0; i < nArgs; i++)
+        if (args[i].p && in_device_memory(args[i].p))
+            return fail(c, HRT_ERR_INVALID_ARG, who + "with dev < 0, " + q.all + " must be host memory (pass the slot of device pointers as dev)");
+    std::vector<float> ms((size_t)nd, 0.f);
+    int rc = for_each_slot(c, nd > 1, q.who, "", [&](int i, hrt_ctx* ec) {
+        return slot(ec, c->dev[(size_t)i], n * i / nd, n * (i + 1) / nd, false, &ms[(size_t)i]);
+    });
+    if (rc != HRT_OK) return rc;
+    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
+    return HRT_OK;
 }
 
 } // namespace
@@ -1946,6 +1959,7 @@ try {
         if (err == hipSuccess) err = hipEventCreateWithFlags(&d.evStage, hipEventDisableTiming);
         for (int f = 0; f < DeviceState::kRing && err == hipSuccess; f++)
             for (int k = 0; k < 4 && err == hipSuccess; k++) err = hipEventCreate(&d.ev[f][k]);
+        for (int e = 0; e < 2 && err == hipSuccess; e++) err = hipEventCreate(&d.q_ev[e]);
         if (err == hipSuccess) { void* p = nullptr; err = hipMalloc(&p, 20 * sizeof(unsigned long long)); d.counters = (unsigned long long*)p; }
         if (err != hipSuccess)
         {
@@ -3135,7 +3149,7 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
     // ---- phase 3: per-tile gather into the caller's host framebuffer.  Each device's copies are issued by its own host
     // thread when the ctx spans several devices: a copy into pageable memory blocks its issuing thread, so one thread
     // would serialise the N gathers.  Into page-locked memory (hrt_host_register) the copies are asynchronous DMA anyway.
-    auto gather_device = [&](DeviceState& d, hrt_ctx* ec) -> int {        // ec == nullptr: errors go to the calling thread's own slot
+    auto gather_device = [&](DeviceState& d, hrt_ctx* ec) -> int {
         HIPCHK(ec, hipSetDevice(d.device_id));
         DReservoir resCur = even ? d.resA : d.resB;
         hipEvent_t* ev = d.ev[d.ring_head];
@@ -3156,21 +3170,8 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
         HIPCHK(ec, hipEventRecord(ev[3], d.stream));
         return HRT_OK;
     };
-    if (out && nd > 1)
-    {
-        std::vector<int> rcs((size_t)nd, HRT_OK);
-        std::vector<std::string> errs((size_t)nd);
-        std::vector<std::thread> workers;
-        for (int i = 0; i < nd; i++)
-            workers.emplace_back([&, i]() {
-                try { rcs[(size_t)i] = gather_device(c->dev[(size_t)i], nullptr); if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error; }
-                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
-            });
-        for (std::thread& t : workers) t.join();
-        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], std::string(who) + ": gather of device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
-    }
-    else
-        for (DeviceState& d : c->dev) { int rc = gather_device(d, c); if (rc != HRT_OK) return rc; }
+    int grc = for_each_slot(c, out && nd > 1, who, "gather of ", [&](int i, hrt_ctx* ec) { return gather_device(c->dev[(size_t)i], ec); });
+    if (grc != HRT_OK) return grc;
     for (DeviceState& d : c->dev) d.ring_head++;
     if (prog)
     {
@@ -3240,7 +3241,6 @@ try {
         d.present_w = outW; d.present_h = outH; d.taa_history_valid = false;
     }
     const int blocks = (int)((outLen + 255) / 256);
-    if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
     HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
     if (pp->mode == HRT_PRESENT_TAAU || reproject)
     {
@@ -3312,7 +3312,6 @@ try {
     if (rc != HRT_OK) return rc;
     const ProjCam from = proj_cam(from_cam ? *from_cam : c->frame_prev_cam), cur = proj_cam(c->frame_cam);
     auto launch = [&](DeviceState& d, hrt_float2* out, int stripN, int stripI, int nRows) -> int {
-        if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
         HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
         const long long lanes = (long long)nRows * W;
         if (lanes > 0)
@@ -3343,14 +3342,9 @@ try {
         for (DeviceState& d : c->dev)
         {
             HIPCHK(c, hipSetDevice(d.device_id));
-            if (d.mv_bytes < bytes)
-            {
-                if (d.mv_mem) { HIPCHK(c, hipStreamSynchronize(d.stream)); (void)hipFree(d.mv_mem); d.mv_mem = nullptr; d.mv_bytes = 0; }
-                HIPCHK(c, hipMalloc(&d.mv_mem, bytes));
-                d.mv_bytes = bytes;
-            }
-            if ((rc = launch(d, (hrt_float2*)d.mv_mem, d.strip_n, d.strip_i, d.n_strips * 8)) != HRT_OK) return rc;      // a ragged last strip: the kernel's row test
-            if ((rc = gather_rows(c, d, mv, (const hrt_float2*)d.mv_mem, W)) != HRT_OK) return rc;
+            if ((rc = d.mv_mem.grow(c, bytes, d.stream)) != HRT_OK) return rc;
+            if ((rc = launch(d, (hrt_float2*)d.mv_mem.p, d.strip_n, d.strip_i, d.n_strips * 8)) != HRT_OK) return rc;      // a ragged last strip: the kernel's row test
+            if ((rc = gather_rows(c, d, mv, (const hrt_float2*)d.mv_mem.p, W)) != HRT_OK) return rc;
         }
         for (DeviceState& d : c->dev) if ((rc = elapsed(d, ms)) != HRT_OK) return rc;
     }
@@ -3435,55 +3429,12 @@ try {
     if (!c) return HRT_ERR_INVALID_ARG;
     if (device_ms) *device_ms = 0.f;
     if (query != HRT_QUERY_CLOSEST && query != HRT_QUERY_OCCLUDED) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: unknown query");
-    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: n must be >= 0");
-    if (n > 0 && (!rays || !results)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: rays and results are needed when n > 0");
-    const int nd = (int)c->dev.size();
-    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: device slot out of range");
-    if (n == 0) return HRT_OK;
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_rays: no scene uploaded (call hrt_scene_upload first)");
     const size_t resBytes = query == HRT_QUERY_CLOSEST ? sizeof(hrt_ray_hit) : sizeof(int32_t);
-    if (dev >= 0)
-    {
-        DeviceState& d = c->dev[(size_t)dev];
-        HIPCHK(c, hipSetDevice(d.device_id));
-        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, results, (size_t)n * resBytes))
-            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: with dev >= 0, rays and results must be device memory of that slot's device, large enough for n");
-        if (((uintptr_t)rays | (uintptr_t)results) & 15) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: device rays and results must be 16-byte aligned");
-        float ms = 0.f;
-        int rc = query_slot(c, *c, d, query, rays, results, 0, n, true, &ms);
-        if (rc != HRT_OK) return rc;
-        if (device_ms) *device_ms = ms;
-        return HRT_OK;
-    }
-    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as the frame's gather)
-    if (in_device_memory(rays) || in_device_memory(results))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_rays: with dev < 0, rays and results must be host memory (pass the slot of device pointers as dev)");
-    std::vector<float> ms((size_t)nd, 0.f);
-    auto part = [&](int i) { return n * i / nd; };
-    if (nd > 1)
-    {
-        std::vector<int> rcs((size_t)nd, HRT_OK);
-        std::vector<std::string> errs((size_t)nd);
-        std::vector<std::thread> workers;
-        for (int i = 0; i < nd; i++)
-            workers.emplace_back([&, i]() {
-                try
-                {
-                    rcs[(size_t)i] = query_slot(nullptr, *c, c->dev[(size_t)i], query, rays, results, part(i), part(i + 1), false, &ms[(size_t)i]);
-                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
-                }
-                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
-            });
-        for (std::thread& t : workers) t.join();
-        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_rays: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
-    }
-    else
-    {
-        int rc = query_slot(c, *c, c->dev[0], query, rays, results, 0, n, false, &ms[0]);
-        if (rc != HRT_OK) return rc;
-    }
-    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
-    return HRT_OK;
+    const QueryArg args[2] = {{rays, sizeof(hrt_ray), 16, false}, {results, resBytes, 16, false}};
+    const QueryDoor door{"hrt_trace_rays", "rays and results", "rays and results", "rays and results must be 16-byte aligned", false};
+    return run_query(c, door, args, 2, n, dev, device_ms, [&](hrt_ctx* ec, DeviceState& d, int64_t begin, int64_t end, bool dev_ptrs, float* ms) {
+        return query_slot(ec, *c, d, query, args, begin, end, dev_ptrs, ms);
+    });
 }
 catch (...) { return on_exception(c, "hrt_trace_rays"); }
 
@@ -3493,72 +3444,25 @@ try {
     if (!c) return HRT_ERR_INVALID_ARG;
     if (device_ms) *device_ms = 0.f;
     if (k < 1 || k > HRT_HITS_MAX) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: k must be in [1, HRT_HITS_MAX]");
-    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: n must be >= 0");
-    if (n > 0 && (!rays || !hits || !counts)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: rays, hits and counts are needed when n > 0");
-    const int nd = (int)c->dev.size();
-    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: device slot out of range");
-    if (n == 0) return HRT_OK;
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_hits: no scene uploaded (call hrt_scene_upload first)");
-    const size_t hitsB = (size_t)n * (size_t)k * sizeof(hrt_ray_hit), intsB = (size_t)n * sizeof(int32_t);
-    if (dev >= 0)
-    {
-        DeviceState& d = c->dev[(size_t)dev];
-        HIPCHK(c, hipSetDevice(d.device_id));
-        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, hits, hitsB) || !on_device(d, counts, intsB) ||
-            (totals && !on_device(d, totals, intsB)))
-            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: with dev >= 0, rays, hits, counts and totals must be device memory of that slot's device, large enough for n");
-        if ((((uintptr_t)rays | (uintptr_t)hits) & 15) || (((uintptr_t)counts | (uintptr_t)totals) & 3))
-            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: device rays and hits must be 16-byte aligned, counts and totals 4-byte aligned");
-        float ms = 0.f;
-        int rc = hits_slot(c, *c, d, rays, k, hits, counts, totals, 0, n, true, &ms);
-        if (rc != HRT_OK) return rc;
-        if (device_ms) *device_ms = ms;
-        return HRT_OK;
-    }
-    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as hrt_trace_rays)
-    if (in_device_memory(rays) || in_device_memory(hits) || in_device_memory(counts) || (totals && in_device_memory(totals)))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_hits: with dev < 0, rays, hits, counts and totals must be host memory (pass the slot of device pointers as dev)");
-    std::vector<float> ms((size_t)nd, 0.f);
-    auto part = [&](int i) { return n * i / nd; };
-    if (nd > 1)
-    {
-        std::vector<int> rcs((size_t)nd, HRT_OK);
-        std::vector<std::string> errs((size_t)nd);
-        std::vector<std::thread> workers;
-        for (int i = 0; i < nd; i++)
-            workers.emplace_back([&, i]() {
-                try
-                {
-                    rcs[(size_t)i] = hits_slot(nullptr, *c, c->dev[(size_t)i], rays, k, hits, counts, totals, part(i), part(i + 1), false, &ms[(size_t)i]);
-                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
-                }
-                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
-            });
-        for (std::thread& t : workers) t.join();
-        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_hits: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
-    }
-    else
-    {
-        int rc = hits_slot(c, *c, c->dev[0], rays, k, hits, counts, totals, 0, n, false, &ms[0]);
-        if (rc != HRT_OK) return rc;
-    }
-    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
-    return HRT_OK;
+    const QueryArg args[4] = {{rays, sizeof(hrt_ray), 16, false}, {hits, (size_t)k * sizeof(hrt_ray_hit), 16, false},
+                              {counts, sizeof(int32_t), 4, false}, {totals, sizeof(int32_t), 4, true}};
+    const QueryDoor door{"hrt_trace_hits", "rays, hits and counts", "rays, hits, counts and totals",
+                         "rays and hits must be 16-byte aligned, counts and totals 4-byte aligned", false};
+    return run_query(c, door, args, 4, n, dev, device_ms, [&](hrt_ctx* ec, DeviceState& d, int64_t begin, int64_t end, bool dev_ptrs, float* ms) {
+        return hits_slot(ec, *c, d, k, args, begin, end, dev_ptrs, ms);
+    });
 }
 catch (...) { return on_exception(c, "hrt_trace_hits"); }
 
-// hrt_trace_paths: rays [begin, end) of one device slot, chunk by chunk on the slot's main stream (after any frame in flight): H2D of the
-// rays, primary kernel into the private G-buffer, fused path stage writing the result records, D2H.  A chunk is whole rows of width
-// keys (at most kQueryChunk slots), or a segment of at most kQueryChunk columns of one row when a row is wider.  *ms += kernel time.
-static int paths_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_frame_params& p, uint32_t flags, const hrt_ray* rays,
-                      hrt_path_result* results, int64_t begin, int64_t end, int64_t first_key, bool dev_ptrs, float* ms)
+// hrt_trace_paths: rays [begin, end) of one device slot, chunk by chunk (ChunkStager): primary kernel into the chunk's private G-buffer,
+// fused path stage writing the result records.  A chunk is whole rows of width keys (at most kQueryChunk slots), or a segment of at
+// most kQueryChunk columns of one row when a row is wider.  Its workspace is the sample groups' scratch, then the G-buffer planes
+// (48 B per slot).
+static int paths_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_frame_params& p, uint32_t flags, const QueryArg* args,
+                      int64_t begin, int64_t end, int64_t first_key, bool dev_ptrs, float* ms)
 {
     HIPCHK(c, hipSetDevice(d.device_id));
-    auto registered = [&](const void* ptr, size_t bytes) {
-        for (const auto& r : cc.pinned) if ((const char*)ptr >= r.first && (const char*)ptr + bytes <= r.first + r.second) return true;
-        return false;
-    };
-    const hipStream_t st = d.stream;
+    ChunkStager s{c, cc, d, args, 2, dev_ptrs};
     const int64_t W = p.width, K1 = first_key + end;
     // the frame's tracer for the scene (render_impl, with the fused path stage): TracerFlat for tiny sphere scenes, the smallest packed
     // walker otherwise (its primary over the second tree where one describes the scene), TracerRef for REFERENCE_LAYOUT
@@ -3576,74 +3480,30 @@ static int paths_slot(hrt_ctx* c, const hrt_ctx& cc, DeviceState& d, const hrt_f
         if (W <= kQueryChunk) { x0 = 0; xw = W; rows = std::min<int64_t>(kQueryChunk / W, (K1 + W - 1) / W - R); }
         else { x0 = (c0 - R * W) / kQueryChunk * kQueryChunk; xw = std::min<int64_t>(kQueryChunk, W - x0); rows = 1; }
         const int64_t c1 = std::min<int64_t>(K1, (R + rows - 1) * W + x0 + xw);
-        const int64_t m = c1 - c0, slots = rows * xw;
-        FrameK k = frame_consts(&p);
-        k.row_begin = (int)R; k.row_end = (int)(R + rows); k.height = k.row_end;
-        TileMap tm;
+        const int64_t slots = rows * xw;
+        L.k = frame_consts(&p);
+        L.k.row_begin = (int)R; L.k.row_end = (int)(R + rows); L.k.height = L.k.row_end;
+        TileMap& tm = L.tm;
         tm.wpb = 4;
         tm.tilesX = (int)((xw + 31) / 32);
         tm.tilesY = (int)((rows + 7) / 8);
         tm.nTiles = tm.tilesX * tm.tilesY;
         tm.band = !cc.small_scene;
-        // sample groups as run_path_stage forms them for a fused frame of this many tiles
-        const int sppAll = p.spp > 1 ? p.spp : 1;
-        const long long waves = (long long)tm.nTiles * tm.wpb, hwSlots = (long long)d.n_cu * 4 * HRT_PT_WAVES;
-        int nGroups = 1;
-        if (p.maxDepth <= 64 && sppAll > 1 && waves < 5 * hwSlots)
-            nGroups = (int)std::min<long long>(std::min(sppAll, 8), (16 * hwSlots + waves - 1) / waves);
-        int perGroup = sppAll;
-        if (nGroups > 1) { perGroup = (sppAll + nGroups - 1) / nGroups; nGroups = (sppAll + perGroup - 1) / perGroup; }
-        const size_t nLocal = (size_t)tm.nTiles * 256;
-        const size_t splitFloats = nGroups > 1 ? ((size_t)sppAll * 3 + (size_t)nGroups * 12) * nLocal : 0;
-        const size_t need = splitFloats * sizeof(float) + (size_t)slots * 48;
-        if (need > d.p_bytes)
-        {
-            if (d.p_mem) { HIPCHK(c, hipStreamSynchronize(st)); (void)hipFree(d.p_mem); d.p_mem = nullptr; d.p_bytes = 0; }
-            HIPCHK(c, hipMalloc(&d.p_mem, need));
-            d.p_bytes = need;
-        }
-        float* split = (float*)d.p_mem;
-        char* gbm = (char*)d.p_mem + splitFloats * sizeof(float);
-        DGBuffer gb;
-        gb.worldPos = (hrt_float3*)gbm; gb.normalWS = gb.worldPos + slots; gb.baseColor = gb.normalWS + slots;
+        // sample groups as a fused frame of this many tiles forms them
+        const int spp = p.spp > 1 ? p.spp : 1;
+        const SampleGroups sg = sample_groups(spp, spp, p.maxDepth, (long long)tm.nTiles * tm.wpb, d.n_cu);
+        const size_t splitBytes = sg.scratchFloats * (size_t)tm.nTiles * 256 * sizeof(float);
+        int rc = s.begin(c0 - first_key, c1 - c0, splitBytes + (size_t)slots * 48);
+        if (rc != HRT_OK) return rc;
+        L.split = (float*)s.work; L.nGroups = sg.nGroups; L.perGroup = sg.perGroup;
+        DGBuffer& gb = L.gb;
+        gb.worldPos = (hrt_float3*)((char*)s.work + splitBytes); gb.normalWS = gb.worldPos + slots; gb.baseColor = gb.normalWS + slots;
         gb.matId = (int32_t*)(gb.baseColor + slots); gb.objId = gb.matId + slots; gb.hitMask = gb.objId + slots;
-
-        if (dev_ptrs)
-        {   // the caller's device buffers hold rays and results: no staging, only the timing events
-            if (!d.q_ev[0]) { HIPCHK(c, hipEventCreate(&d.q_ev[0])); HIPCHK(c, hipEventCreate(&d.q_ev[1])); }
-        }
-        else
-        {
-            int rc = ensure_query(c, d, m, true);
-            if (rc != HRT_OK) return rc;
-        }
-        char* qbase = (char*)d.q_mem;
-        const hrt_ray* src = rays + (c0 - first_key);
-        hrt_path_result* dst = results + (c0 - first_key);
-        const bool rayReg = !dev_ptrs && registered(src, (size_t)m * sizeof(hrt_ray));
-        const bool resReg = !dev_ptrs && registered(dst, (size_t)m * sizeof(hrt_path_result));
-        char* hostRays = (char*)d.q_host;
-        char* hostRes = (char*)d.q_host + (size_t)d.q_host_cap * 32;
-        PathsK q;
+        PathsK& q = L.q;
         q.k0 = (int)c0; q.k1 = (int)c1; q.base = (int)(R * W + x0); q.x0 = (int)x0; q.xw = (int)xw;
-        if (dev_ptrs) { q.rays = src; q.out = dst; }
-        else
-        {
-            q.rays = (const hrt_ray*)qbase;
-            q.out = (hrt_path_result*)(qbase + (size_t)d.q_cap * 48);
-            if (!rayReg) std::memcpy(hostRays, src, (size_t)m * sizeof(hrt_ray));
-            HIPCHK(c, hipMemcpyAsync(qbase, rayReg ? (const void*)src : (const void*)hostRays, (size_t)m * sizeof(hrt_ray), hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(c, hipEventRecord(d.q_ev[0], st));
-        L.k = k; L.tm = tm; L.q = q; L.gb = gb; L.split = split; L.nGroups = nGroups; L.perGroup = perGroup;
-        HIPCHK(c, paths_launch(L, st));
-        HIPCHK(c, hipEventRecord(d.q_ev[1], st));
-        if (!dev_ptrs) HIPCHK(c, hipMemcpyAsync(resReg ? (void*)dst : (void*)hostRes, q.out, (size_t)m * sizeof(hrt_path_result), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, d.q_ev[0], d.q_ev[1]));
-        *ms += t;
-        if (!dev_ptrs && !resReg) std::memcpy(dst, hostRes, (size_t)m * sizeof(hrt_path_result));
+        q.rays = (const hrt_ray*)s.dev[0]; q.out = (hrt_path_result*)s.dev[1];
+        HIPCHK(c, paths_launch(L, d.stream));
+        if ((rc = s.end(ms)) != HRT_OK) return rc;
         c0 = c1;
     }
     return HRT_OK;
@@ -3662,56 +3522,14 @@ try {
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: ReSTIR reuse needs a frame's reservoirs: set enableTemporalReuse and enableSpatialReuse to 0");
     if (p->width <= 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: params->width must be positive");
     if (p->maxDepth < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: maxDepth must be >= 0");
-    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: n must be >= 0");
+    if (n < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: n must be >= 0");      // here too: the key range below is tested on a valid n
     if (first_key < 0) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: first_key must be >= 0");
     if (first_key > 0x7FFFFFFFLL - n) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: first_key + n exceeds 2^31 - 1 (keys are int pixel indices)");
-    if (n > 0 && (!rays || !results)) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: rays and results are needed when n > 0");
-    const int nd = (int)c->dev.size();
-    if (dev >= nd) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: device slot out of range");
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_trace_paths: no scene uploaded (call hrt_scene_upload first)");
-    if (n == 0) return HRT_OK;
-    if (dev >= 0)
-    {
-        DeviceState& d = c->dev[(size_t)dev];
-        HIPCHK(c, hipSetDevice(d.device_id));
-        if (!on_device(d, rays, (size_t)n * sizeof(hrt_ray)) || !on_device(d, results, (size_t)n * sizeof(hrt_path_result)))
-            return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: with dev >= 0, rays and results must be device memory of that slot's device, large enough for n");
-        if (((uintptr_t)rays | (uintptr_t)results) & 15) return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: device rays and results must be 16-byte aligned");
-        float ms = 0.f;
-        int rc = paths_slot(c, *c, d, *p, flags, rays, results, 0, n, first_key, true, &ms);
-        if (rc != HRT_OK) return rc;
-        if (device_ms) *device_ms = ms;
-        return HRT_OK;
-    }
-    // host memory: contiguous parts, one per slot, each issued by a thread of its own when the ctx spans several (as hrt_trace_rays)
-    if (in_device_memory(rays) || in_device_memory(results))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_trace_paths: with dev < 0, rays and results must be host memory (pass the slot of device pointers as dev)");
-    std::vector<float> ms((size_t)nd, 0.f);
-    auto part = [&](int i) { return n * i / nd; };
-    if (nd > 1)
-    {
-        std::vector<int> rcs((size_t)nd, HRT_OK);
-        std::vector<std::string> errs((size_t)nd);
-        std::vector<std::thread> workers;
-        for (int i = 0; i < nd; i++)
-            workers.emplace_back([&, i]() {
-                try
-                {
-                    rcs[(size_t)i] = paths_slot(nullptr, *c, c->dev[(size_t)i], *p, flags, rays, results, part(i), part(i + 1), first_key, false, &ms[(size_t)i]);
-                    if (rcs[(size_t)i] != HRT_OK) errs[(size_t)i] = g_create_error;
-                }
-                catch (...) { rcs[(size_t)i] = HRT_ERR_OUT_OF_MEMORY; }
-            });
-        for (std::thread& t : workers) t.join();
-        for (int i = 0; i < nd; i++) if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], "hrt_trace_paths: device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
-    }
-    else
-    {
-        int rc = paths_slot(c, *c, c->dev[0], *p, flags, rays, results, 0, n, first_key, false, &ms[0]);
-        if (rc != HRT_OK) return rc;
-    }
-    if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
-    return HRT_OK;
+    const QueryArg args[2] = {{rays, sizeof(hrt_ray), 16, false}, {results, sizeof(hrt_path_result), 16, false}};
+    const QueryDoor door{"hrt_trace_paths", "rays and results", "rays and results", "rays and results must be 16-byte aligned", true};
+    return run_query(c, door, args, 2, n, dev, device_ms, [&](hrt_ctx* ec, DeviceState& d, int64_t begin, int64_t end, bool dev_ptrs, float* ms) {
+        return paths_slot(ec, *c, d, *p, flags, args, begin, end, first_key, dev_ptrs, ms);
+    });
 }
 catch (...) { return on_exception(c, "hrt_trace_paths"); }
 

@@ -696,65 +696,42 @@ class RTRenderer(FrameHost):
         q = _QUERIES.get(query)
         if q is None:
             raise ValueError("query must be one of %s, not %r" % (sorted(_QUERIES), query))
-        if type(origins).__module__.split(".")[0] == "torch" or type(dirs).__module__.split(".")[0] == "torch":
+        if _torch_inputs(origins, dirs):
             return self._trace_rays_torch(q, origins, dirs, tmax, slot)
-        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
-        if slot is not None:
-            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        o, d = _host_rays(origins, dirs, slot)
         n = o.shape[0]
-        rays = np.zeros((n, 8), np.float32)
-        rays[:, 0:3], rays[:, 4:7] = o, d
-        rays[:, 3] = _tmax_arg(tmax, n)
+        rays = _pack_host_rays(o, d, tmax)
         out = np.zeros(n, T.np_dtype(T.RayHit)) if q == T.QUERY_CLOSEST else np.zeros(n, np.int32)
         ms = C.c_float(0.0)
         self._check(self._L.hrt_trace_rays(self._ctx, q, rays.ctypes.data if n else None, n, out.ctypes.data if n else None, -1, C.byref(ms)))
         self.last_query_ms = ms.value
         return out
 
-    def _trace_rays_torch(self, q, origins, dirs, tmax, slot):
-        import torch                                       # lazy: the host path needs no torch
-        if not (isinstance(origins, torch.Tensor) and isinstance(dirs, torch.Tensor)):
-            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
-        for name, a in (("origins", origins), ("dirs", dirs)):
-            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
-            if a.device.type != "cuda":
-                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
-        if origins.shape != dirs.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
-        if origins.device != dirs.device:
-            raise ValueError("origins and dirs live on different devices")
-        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
+    def _torch_slot(self, device, slot):
+        """The device slot of this renderer that torch device `device` is (`slot` picks one of several on it)."""
+        import torch
+        dev = device.index if device.index is not None else torch.cuda.current_device()
         slots = [i for i, d in enumerate(self.device_ids) if d == dev]
         if slot is None:
             if not slots:
                 raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
-            slot = slots[0]
-        elif slot not in slots:
+            return slots[0]
+        if slot not in slots:
             raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
-        n = origins.shape[0]
-        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
-        rays[:, 0:3], rays[:, 4:7] = origins, dirs
-        if tmax is None or isinstance(tmax, (int, float, np.floating)):
-            rays[:, 3] = float("inf") if tmax is None else float(np.float32(tmax))
-        else:
-            tm = torch.as_tensor(tmax, device=origins.device)
-            if tm.dtype != torch.float32 or tuple(tm.shape) != (n,):
-                raise ValueError("tmax must be a float or an (n,) float32 array")
-            rays[:, 3] = tm
+        return slot
+
+    def _trace_rays_torch(self, q, origins, dirs, tmax, slot):
+        import torch                                       # lazy: the host path needs no torch
+        n, tm = _check_torch_rays(origins, dirs, tmax)
+        slot = self._torch_slot(origins.device, slot)
+        rays = _pack_torch_rays(origins, dirs, tm)
         out = torch.zeros((n, 12) if q == T.QUERY_CLOSEST else (n,), dtype=torch.float32 if q == T.QUERY_CLOSEST else torch.int32,
                           device=origins.device)
         torch.cuda.synchronize(origins.device)               # the library works on its own streams
         ms = C.c_float(0.0)
         self._check(self._L.hrt_trace_rays(self._ctx, q, rays.data_ptr() if n else None, n, out.data_ptr() if n else None, slot, C.byref(ms)))
         self.last_query_ms = ms.value
-        if q != T.QUERY_CLOSEST:
-            return out
-        ints = out[:, 8:12].view(torch.int32)
-        return dict(t=out[:, 0], normal=out[:, 1:4], albedo=out[:, 4:7], ior=out[:, 7],
-                    objId=ints[:, 0], shade=ints[:, 1], instance=ints[:, 2], prim=ints[:, 3])
+        return _hit_dict(out) if q == T.QUERY_CLOSEST else out
 
     def trace_hits(self, origins, dirs, k, tmax=None, totals=False, slot=None):
         """The k nearest accepted hits along each ray (hrt_trace_hits): ShadowOcclusion's walk (SceneDeviceViews.cs:89-121) run to the
@@ -770,20 +747,11 @@ class RTRenderer(FrameHost):
         if not 1 <= k <= T.HITS_MAX:
             raise ValueError("k must be in [1, %d], got %d" % (T.HITS_MAX, k))
         totals = bool(totals)
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (origins, dirs)]
-        if any(is_torch) and not all(is_torch):
-            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
-        if all(is_torch):
+        if _torch_inputs(origins, dirs):
             return self._trace_hits_torch(origins, dirs, k, tmax, totals, slot)
-        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
-        if slot is not None:
-            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        o, d = _host_rays(origins, dirs, slot)
         n = o.shape[0]
-        rays = np.zeros((n, 8), np.float32)
-        rays[:, 0:3], rays[:, 4:7] = o, d
-        rays[:, 3] = _tmax_arg(tmax, n)
+        rays = _pack_host_rays(o, d, tmax)
         hits = np.zeros((n, k), T.np_dtype(T.RayHit))
         counts = np.zeros(n, np.int32)
         tot = np.zeros(n, np.int32) if totals else None
@@ -795,34 +763,9 @@ class RTRenderer(FrameHost):
 
     def _trace_hits_torch(self, origins, dirs, k, tmax, totals, slot):
         import torch
-        for name, a in (("origins", origins), ("dirs", dirs)):
-            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
-            if a.device.type != "cuda":
-                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
-        if origins.shape != dirs.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
-        if origins.device != dirs.device:
-            raise ValueError("origins and dirs live on different devices")
-        n = origins.shape[0]
-        if not (tmax is None or isinstance(tmax, (int, float, np.floating))):
-            tm = torch.as_tensor(tmax, device=origins.device)
-            if tm.dtype != torch.float32 or tuple(tm.shape) != (n,):
-                raise ValueError("tmax must be a float or an (n,) float32 array")
-        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
-        slots = [i for i, d in enumerate(self.device_ids) if d == dev]
-        if slot is None:
-            if not slots:
-                raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
-            slot = slots[0]
-        elif slot not in slots:
-            raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
-        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
-        rays[:, 0:3], rays[:, 4:7] = origins, dirs
-        if tmax is None or isinstance(tmax, (int, float, np.floating)):
-            rays[:, 3] = float("inf") if tmax is None else float(np.float32(tmax))
-        else:
-            rays[:, 3] = tm
+        n, tm = _check_torch_rays(origins, dirs, tmax)
+        slot = self._torch_slot(origins.device, slot)
+        rays = _pack_torch_rays(origins, dirs, tm)
         out = torch.zeros((n, k, 12), dtype=torch.float32, device=origins.device)
         counts = torch.zeros(n, dtype=torch.int32, device=origins.device)
         tot = torch.zeros(n, dtype=torch.int32, device=origins.device) if totals else None
@@ -831,9 +774,7 @@ class RTRenderer(FrameHost):
         self._check(self._L.hrt_trace_hits(self._ctx, rays.data_ptr() if n else None, n, k, out.data_ptr() if n else None,
                                            counts.data_ptr() if n else None, tot.data_ptr() if (n and totals) else None, slot, C.byref(ms)))
         self.last_query_ms = ms.value
-        ints = out[:, :, 8:12].view(torch.int32)
-        return dict(t=out[:, :, 0], normal=out[:, :, 1:4], albedo=out[:, :, 4:7], ior=out[:, :, 7],
-                    objId=ints[:, :, 0], shade=ints[:, :, 1], instance=ints[:, :, 2], prim=ints[:, :, 3], counts=counts, totals=tot)
+        return dict(_hit_dict(out), counts=counts, totals=tot)
 
     def trace_paths(self, origins, dirs, params, first_key=0, flags=0, slot=None):
         """PathTraceKernel (RTRay.cs:203-325) along caller rays (hrt_trace_paths): ray i is shaded as pixel key j = first_key + i of
@@ -855,21 +796,13 @@ class RTRenderer(FrameHost):
         first_key = int(first_key)
         if first_key < 0:
             raise ValueError("first_key must be >= 0")
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (origins, dirs)]
-        if any(is_torch) and not all(is_torch):
-            raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
-        if all(is_torch):
+        if _torch_inputs(origins, dirs):
             return self._trace_paths_torch(origins, dirs, params, first_key, flags, slot)
-        o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
-        if o.shape != d.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
-        if slot is not None:
-            raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+        o, d = _host_rays(origins, dirs, slot)
         n = o.shape[0]
         if first_key + n > 0x7FFFFFFF:
             raise ValueError("first_key + n exceeds 2^31 - 1")
-        rays = np.zeros((n, 8), np.float32)
-        rays[:, 0:3], rays[:, 4:7] = o, d
+        rays = _pack_host_rays(o, d, _NO_TMAX)
         out = np.zeros(n, T.np_dtype(T.PathResult))
         ms = C.c_float(0.0)
         self._check(self._L.hrt_trace_paths(self._ctx, C.byref(params), flags, rays.ctypes.data if n else None, n, first_key,
@@ -879,28 +812,11 @@ class RTRenderer(FrameHost):
 
     def _trace_paths_torch(self, origins, dirs, params, first_key, flags, slot):
         import torch                                       # lazy: the host path needs no torch
-        for name, a in (("origins", origins), ("dirs", dirs)):
-            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
-            if a.device.type != "cuda":
-                raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
-        if origins.shape != dirs.shape:
-            raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
-        if origins.device != dirs.device:
-            raise ValueError("origins and dirs live on different devices")
-        n = origins.shape[0]
+        n, _ = _check_torch_rays(origins, dirs, _NO_TMAX)
         if first_key + n > 0x7FFFFFFF:
             raise ValueError("first_key + n exceeds 2^31 - 1")
-        dev = origins.device.index if origins.device.index is not None else torch.cuda.current_device()
-        slots = [i for i, d in enumerate(self.device_ids) if d == dev]
-        if slot is None:
-            if not slots:
-                raise ValueError("no device slot of this renderer is on cuda:%d (slots: %s)" % (dev, self.device_ids))
-            slot = slots[0]
-        elif slot not in slots:
-            raise ValueError("device slot %r is not on cuda:%d (slots: %s)" % (slot, dev, self.device_ids))
-        rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
-        rays[:, 0:3], rays[:, 4:7] = origins, dirs
+        slot = self._torch_slot(origins.device, slot)
+        rays = _pack_torch_rays(origins, dirs, _NO_TMAX)
         out = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
         torch.cuda.synchronize(origins.device)               # the library works on its own streams
         ms = C.c_float(0.0)
@@ -1017,6 +933,77 @@ def _tmax_arg(tmax, n):
     if t.dtype != np.float32 or t.shape != (n,):
         raise ValueError("tmax must be a float or an (n,) float32 array, got %s %s" % (t.dtype, t.shape))
     return t
+
+
+# what trace_rays / trace_hits / trace_paths and their torch twins share
+_NO_TMAX = object()            # trace_paths: its rays carry no tmax, the column stays 0
+
+
+def _torch_inputs(origins, dirs):
+    """True: both are torch tensors (device path); False: neither is (host path).  A mix is refused."""
+    is_torch = [type(a).__module__.split(".")[0] == "torch" for a in (origins, dirs)]
+    if any(is_torch) and not all(is_torch):
+        raise TypeError("origins and dirs must both be numpy arrays or both torch tensors")
+    return all(is_torch)
+
+
+def _host_rays(origins, dirs, slot):
+    o, d = _rays_arg(origins, "origins"), _rays_arg(dirs, "dirs")
+    if o.shape != d.shape:
+        raise ValueError("origins and dirs differ in shape: %s vs %s" % (o.shape, d.shape))
+    if slot is not None:
+        raise ValueError("slot selects the device of torch inputs; host arrays are split over every device slot")
+    return o, d
+
+
+def _pack_host_rays(o, d, tmax):
+    """(n, 8) float32: hrt_ray's origin, tmax, direction, pad."""
+    n = o.shape[0]
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:3], rays[:, 4:7] = o, d
+    if tmax is not _NO_TMAX:
+        rays[:, 3] = _tmax_arg(tmax, n)
+    return rays
+
+
+def _check_torch_rays(origins, dirs, tmax):
+    """Returns n and what goes into the tmax column (a float or an (n,) tensor on the rays' device)."""
+    import torch                                       # lazy: the host path needs no torch
+    for name, a in (("origins", origins), ("dirs", dirs)):
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError("%s must be an (n, 3) float32 tensor, got %s %s" % (name, tuple(a.shape), a.dtype))
+        if a.device.type != "cuda":
+            raise ValueError("%s: torch inputs must live on a GPU (numpy arrays take the host path)" % name)
+    if origins.shape != dirs.shape:
+        raise ValueError("origins and dirs differ in shape: %s vs %s" % (tuple(origins.shape), tuple(dirs.shape)))
+    if origins.device != dirs.device:
+        raise ValueError("origins and dirs live on different devices")
+    n = origins.shape[0]
+    if tmax is _NO_TMAX:
+        return n, tmax
+    if tmax is None or isinstance(tmax, (int, float, np.floating)):
+        return n, float("inf") if tmax is None else float(np.float32(tmax))
+    tm = torch.as_tensor(tmax, device=origins.device)
+    if tm.dtype != torch.float32 or tuple(tm.shape) != (n,):
+        raise ValueError("tmax must be a float or an (n,) float32 array")
+    return n, tm
+
+
+def _pack_torch_rays(origins, dirs, tm):
+    import torch
+    rays = torch.zeros((origins.shape[0], 8), dtype=torch.float32, device=origins.device)
+    rays[:, 0:3], rays[:, 4:7] = origins, dirs
+    if tm is not _NO_TMAX:
+        rays[:, 3] = tm
+    return rays
+
+
+def _hit_dict(out):
+    """The fields of T.RayHit as views of a (..., 12) float32 tensor of records."""
+    import torch
+    ints = out[..., 8:12].view(torch.int32)
+    return dict(t=out[..., 0], normal=out[..., 1:4], albedo=out[..., 4:7], ior=out[..., 7],
+                objId=ints[..., 0], shade=ints[..., 1], instance=ints[..., 2], prim=ints[..., 3])
 
 
 class SceneManager:

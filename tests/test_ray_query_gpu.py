@@ -564,3 +564,80 @@ def test_error_codes(renderer, hrt_lib):
     assert L.hrt_trace_rays(ctx, 1, ray, 4, hits, 0, None) == -1
     assert L.hrt_trace_rays(ctx, 0, None, 0, None, -1, None) == 0              # n == 0: nothing to do
     assert L.hrt_trace_rays(ctx, 0, ray, 4, hits, -1, C.byref(ms)) == 0 and ms.value >= 0.0
+
+
+# ------------------------------------------------------------------ 9. the staging the three caller-ray queries share
+def _pack(o, d, tmax):
+    rays = np.zeros((len(o), 8), np.float32)
+    rays[:, 0:3], rays[:, 4:7], rays[:, 3] = o, d, tmax
+    return rays
+
+
+def _three_queries(L, ctx, p, rays, n, k, nh, out=None):
+    """hrt_trace_rays (both queries) and hrt_trace_paths over the first n of rays, hrt_trace_hits with totals over the first nh, through
+    the C entry points with the caller's own arrays; returns them (freshly allocated unless `out` passes a set in)."""
+    res = out or dict(closest=np.zeros(n, T.np_dtype(T.RayHit)), occluded=np.zeros(n, np.int32), hits=np.zeros((nh, k), T.np_dtype(T.RayHit)),
+                      counts=np.zeros(nh, np.int32), totals=np.zeros(nh, np.int32), paths=np.zeros(n, T.np_dtype(T.PathResult)))
+    ptr = lambda name: res[name].ctypes.data
+    assert L.hrt_trace_rays(ctx, T.QUERY_CLOSEST, rays.ctypes.data, n, ptr("closest"), -1, None) == 0
+    assert L.hrt_trace_hits(ctx, rays.ctypes.data, nh, k, ptr("hits"), ptr("counts"), ptr("totals"), -1, None) == 0
+    assert L.hrt_trace_paths(ctx, C.byref(p), 0, rays.ctypes.data, n, 0, ptr("paths"), -1, None) == 0
+    assert L.hrt_trace_rays(ctx, T.QUERY_OCCLUDED, rays.ctypes.data, n, ptr("occluded"), -1, None) == 0
+    return res
+
+
+def _assert_same_bytes(a, b, what):
+    for name in a:
+        assert a[name].tobytes() == b[name].tobytes(), "%s: %s" % (what, name)
+
+
+def _staging_case(rng, n):
+    p = scenes.frame_params(scenes.CONFIGS[2], *H.host_funcs("hrt"), width=1920, height=1200, spp=4)
+    o, d = _camera_rays(p, rng.integers(0, p.width * p.height, n))
+    d[::3] = rng.standard_normal((len(d[::3]), 3)).astype(np.float32)
+    return p, _pack(o, d, _tmax_mix(rng, n))
+
+
+@pytest.mark.timeout(900)
+def test_registered_host_arrays_give_the_same_bytes(orc, renderer, hrt_lib):
+    """A host-path call whose arrays the caller page-locked (hrt_host_register) copies straight from and into them, without the pinned
+    staging: the same bytes as the pageable call, for the three queries, with more rays (and, at k = 4, more hit slots) than a chunk."""
+    _commit(renderer, _oracle_scene(orc, scenes.build_config2))
+    n, nh = T.QUERY_CHUNK + 777, T.QUERY_CHUNK // 4 + 777
+    p, rays = _staging_case(np.random.default_rng(21), n)
+    ref = _three_queries(hrt_lib, renderer._ctx, p, rays, n, 4, nh)
+    got = {name: np.zeros_like(a) for name, a in ref.items()}
+    pinned = [rays] + list(got.values())
+    renderer.register_host(pinned)
+    try:
+        _three_queries(hrt_lib, renderer._ctx, p, rays, n, 4, nh, out=got)
+    finally:
+        renderer.unregister_host(pinned)
+    assert ref["counts"].any() and ref["occluded"].any()
+    _assert_same_bytes(ref, got, "registered")
+    # only some of a call's arrays registered: each array decides for itself
+    some = {name: np.zeros_like(a) for name, a in ref.items()}
+    pinned = [some["hits"], some["paths"]]
+    renderer.register_host(pinned)
+    try:
+        _three_queries(hrt_lib, renderer._ctx, p, rays, n, 4, nh, out=some)
+    finally:
+        renderer.unregister_host(pinned)
+    _assert_same_bytes(ref, some, "partly registered")
+
+
+@pytest.mark.timeout(900)
+def test_alternating_queries_share_one_context(orc, renderer, hrt_lib):
+    """One context calling the three queries in turn, small then large then small (k = 16 after hrt_trace_rays, radiance after both),
+    gives what a fresh context gives for each size: the staging is carved anew for every chunk of every query."""
+    desc, keep = _commit(renderer, _oracle_scene(orc, scenes.build_config2))
+    sizes = (300, T.QUERY_CHUNK // 16 + 4097, 65)
+    p, rays = _staging_case(np.random.default_rng(22), max(sizes))
+    got = [_three_queries(hrt_lib, renderer._ctx, p, rays, n, 16, n) for n in sizes]
+    for n, g in zip(sizes, got):
+        fresh = engine.RTRenderer([0])
+        try:
+            fresh.commit(desc)
+            _assert_same_bytes(_three_queries(hrt_lib, fresh._ctx, p, rays, n, 16, n), g, "n=%d" % n)
+        finally:
+            fresh.close()
