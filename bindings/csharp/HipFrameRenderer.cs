@@ -60,13 +60,28 @@ namespace ILGPU_Raytracing.Engine
 
         /// <summary>Presents the last frame again (or for the first time) with the given mode; the history follows the frames that
         /// were actually resolved, so skipping or repeating a present is safe in every mode.</summary>
-        public ReadOnlySpan<int> Present(int outW, int outH, HrtPresentMode mode)
+        public ReadOnlySpan<int> Present(int outW, int outH, HrtPresentMode mode, bool denoised = false)
         {
             if (_display.Length != outW * outH) _display = new int[outW * outH];
-            var pp = new HrtPresentParams { out_width = outW, out_height = outH, mode = (int)mode };   // tunables <= 0: the reference's 0.075 / 0.10 / 1.25
+            var pp = new HrtPresentParams { out_width = outW, out_height = outH, mode = (int)mode | (denoised ? HipRaytrace.HRT_PRESENT_DENOISED : 0) };   // tunables <= 0: the reference's 0.075 / 0.10 / 1.25
             fixed (int* dst = _display)
                 HipRaytrace.Check(_ctx, HipRaytrace.hrt_present(_ctx, &pp, dst));
             return _display;
+        }
+
+        /// <summary>Edge-avoiding a-trous denoiser over the radiance of the last full-image frame, guided by its G-buffer (hrt_denoise).
+        /// The frame is left as it is; Present(..., denoised: true) resolves the denoised colour until the next frame.  radiance / color
+        /// (internal size, either may be empty) receive the denoised planes.  Returns the HIP-event time of the kernels in ms.</summary>
+        public float Denoise(Span<Float3> radiance = default, Span<int> color = default, int iterations = 0, bool demodulate = true,
+                             float sigmaColor = 0f, float sigmaNormal = 0f, float sigmaPlane = 0f)
+        {
+            var dp = new HrtDenoiseParams { iterations = iterations, flags = (uint)(demodulate ? HrtDenoiseFlags.None : HrtDenoiseFlags.NoDemodulate),
+                                            sigma_color = sigmaColor, sigma_normal = sigmaNormal, sigma_plane = sigmaPlane };
+            float ms = 0f;
+            fixed (Float3* r = radiance)
+            fixed (int* c = color)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_denoise(_ctx, &dp, radiance.IsEmpty ? null : r, color.IsEmpty ? null : c, &ms));
+            return ms;
         }
 
         /// <summary>Camera motion vectors of the last full-image frame (hrt_motion_vectors), one per internal pixel, in pixels: where the

@@ -52,6 +52,10 @@ namespace ILGPU_Raytracing.Engine
     [StructLayout(LayoutKind.Sequential)]
     public struct HrtPresentParams { public int out_width, out_height, mode; public float feedback, sharpness, clampK; }   // mode: HrtPresentMode
     public enum HrtPresentMode { Resample = 0, Taau = 1, TaauReproject = 2 }   // hrt_present_mode: blit / bilinear, TAAU, TAAU with camera reprojection
+    // hrt_denoise_params: iterations 1..8 (0: 5), flags HrtDenoiseFlags, sigmas <= 0: 4.0 / 0.5 / 0.02
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtDenoiseParams { public int iterations; public uint flags; public float sigma_color, sigma_normal, sigma_plane; }
+    [Flags] public enum HrtDenoiseFlags : uint { None = 0, NoDemodulate = 1 }
 
     [StructLayout(LayoutKind.Sequential)]
     public unsafe struct HrtOutputs               // host destinations of one frame, any may be null
@@ -126,6 +130,10 @@ namespace ILGPU_Raytracing.Engine
         [DllImport(Lib)] public static extern int hrt_render_progressive(IntPtr ctx, HrtFrameParams* p, HrtRenderOpts* opts, int sampleBegin, HrtOutputs* outputs, HrtStats* stats);
         [DllImport(Lib)] public static extern int hrt_present(IntPtr ctx, HrtPresentParams* p, int* outColorHost);
         [DllImport(Lib)] public static extern int hrt_present_time(IntPtr ctx, float* ms);
+        public const int HRT_PRESENT_DENOISED = 0x100;   // OR into HrtPresentParams.mode: resolve the denoised colour of the last hrt_denoise
+        // a-trous denoiser over the last full-image frame; either host destination may be null (the planes stay on device slot 0)
+        [DllImport(Lib)] public static extern int hrt_denoise(IntPtr ctx, HrtDenoiseParams* p, Float3* outRadianceHost, int* outColorHost, float* deviceMs);
+        [DllImport(Lib)] public static extern int hrt_denoised_buffers(IntPtr ctx, IntPtr* radiance, IntPtr* color);
         // camera motion vectors of the last full-image frame, in pixels; fromCam null: the frame's prevCam; dev < 0 host memory, 0 device memory of slot 0
         [DllImport(Lib)] public static extern int hrt_motion_vectors(IntPtr ctx, Camera* fromCam, Float2* mv, int dev, float* deviceMs);
         [DllImport(Lib)] public static extern int hrt_synchronize(IntPtr ctx, HrtStats* stats);

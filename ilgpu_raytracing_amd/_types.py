@@ -163,6 +163,15 @@ class PresentParams(C.Structure):
 
 
 PRESENT_RESAMPLE, PRESENT_TAAU, PRESENT_TAAU_REPROJECT = 0, 1, 2      # hrt_present_mode
+PRESENT_DENOISED = 0x100            # OR into PresentParams.mode: resolve the denoised colour of hrt_denoise instead of the frame's
+
+
+class DenoiseParams(C.Structure):     # hrt_denoise_params
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
+DENOISE_NO_DEMODULATE = 1             # hrt_denoise_flags
 
 
 class Ray(C.Structure):               # hrt_ray: a ray of hrt_trace_rays

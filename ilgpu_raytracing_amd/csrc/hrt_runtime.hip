@@ -28,6 +28,7 @@
 #include "hrt_query.hpp"
 #include "hrt_paths.hpp"
 #include "hrt_hits.hpp"
+#include "hrt_denoise.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
 #include "../../include/hrt_test_hooks.h"
@@ -604,6 +605,12 @@ struct DeviceState {
     hipEvent_t q_ev[2] = {};                   // bracket the kernels of a chunk; hrt_present and hrt_motion_vectors time theirs with them too
     // hrt_motion_vectors, host path: the slot's vectors before they are gathered (8 B per pixel, global pixel index)
     Scratch mv_mem;
+    // hrt_denoise, device slot 0 only: guide records (32 B per pixel), two colour planes (16 B each), then the two result planes
+    // (denoised radiance 12 B, packed colour 4 B); dn_pix = the frame size they were allocated for
+    Scratch dn_mem;
+    int64_t dn_pix = 0;
+    hrt_float3* dn_radiance = nullptr;
+    int32_t* dn_color = nullptr;
 };
 
 } // namespace
@@ -631,6 +638,8 @@ struct hrt_ctx {
     int64_t scene_count[15] = {};
     int width = 0, height = 0;
     hrt_camera frame_cam{}, frame_prev_cam{};  // cam / prevCam of the last frame call (what gb_worldPos was rendered from)
+    uint64_t frame_serial = 0;                 // counts frame calls and scene uploads: what the denoised planes are checked against
+    uint64_t dn_serial = 0;                    // frame_serial of the frame hrt_denoise last ran on (0: never)
     long long max_resident_paths = 0;          // hrt_set_workspace_limit: 0 = kWfMaxPaths
     std::vector<std::pair<char*, size_t>> pinned;   // hrt_host_register: page-locked ranges of the caller (gather targets)
     // the progressive frame a continuation (hrt_render_progressive with sample_begin > 0) may extend: what its last call rendered.
@@ -1669,6 +1678,7 @@ void free_query(DeviceState& d)
     d.q_dev.release();
     d.q_pin.release(true);
     d.mv_mem.release();
+    d.dn_mem.release(); d.dn_pix = 0; d.dn_radiance = nullptr; d.dn_color = nullptr;
     for (hipEvent_t& e : d.q_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
 }
 
@@ -2054,6 +2064,7 @@ int hrt_scene_upload(hrt_ctx* c, const hrt_scene_desc* s)
 try {
     if (!c) return HRT_ERR_INVALID_ARG;
     c->prog.valid = false;                     // a progressive frame cannot be continued across this call
+    c->frame_serial++;                         // ... and denoised planes no longer belong to what is on the device
     if (!s) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: scene is NULL");
     const void* src[15] = {s->tlasNodes, s->tlasInstanceIndices, s->instances, s->blasNodes, s->spherePrimIdx, s->spheres,
                            s->triPrimIdx, s->meshPositions, s->meshTris, s->meshTexcoords, s->meshTriUVs, s->triMatIndex,
@@ -2999,6 +3010,7 @@ static int render_impl(hrt_ctx* c, const hrt_frame_params* p, const hrt_render_o
     }
     c->width = p->width; c->height = p->height;
     c->frame_cam = p->cam; c->frame_prev_cam = p->prevCam;
+    c->frame_serial++;
 
     // 8-row strips of [rb,re) are dealt round-robin: this call owns strips s % sn == si, and
     // device i of the ctx takes every nd-th of those (sky rows are cheap, geometry rows are
@@ -3212,13 +3224,19 @@ try {
     if (!pp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: params is NULL");
     if (pp->out_width <= 0 || pp->out_height <= 0 || (int64_t)pp->out_width * pp->out_height > 0x7FFFFFFFLL)
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: output size must be positive");
-    if (pp->mode != HRT_PRESENT_RESAMPLE && pp->mode != HRT_PRESENT_TAAU && pp->mode != HRT_PRESENT_TAAU_REPROJECT)
+    const bool denoised = (pp->mode & HRT_PRESENT_DENOISED) != 0;
+    const int mode = pp->mode & ~HRT_PRESENT_DENOISED;
+    if (mode != HRT_PRESENT_RESAMPLE && mode != HRT_PRESENT_TAAU && mode != HRT_PRESENT_TAAU_REPROJECT)
         return fail(c, HRT_ERR_INVALID_ARG, "hrt_present: unknown mode");
-    const bool reproject = pp->mode == HRT_PRESENT_TAAU_REPROJECT;
+    const bool reproject = mode == HRT_PRESENT_TAAU_REPROJECT;
     const int nd = (int)c->dev.size();
     DeviceState& d = c->dev[0];
     if (d.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, "hrt_present: no frame rendered yet");
     if (d.strip_n != nd || d.row_begin != 0 || d.row_end != c->height) return fail(c, HRT_ERR_INVALID_STATE, "hrt_present: the last frame was a partial tile");
+    if (denoised && (!d.dn_color || c->dn_serial != c->frame_serial || d.dn_pix != d.nPix))
+        return fail(c, HRT_ERR_INVALID_STATE, "hrt_present: HRT_PRESENT_DENOISED, but the denoised colour does not belong to the last frame "
+                    "(call hrt_denoise after the frame, scene upload or resize)");
+    const int32_t* lowColor = denoised ? d.dn_color : d.fb.color;      // the one thing the flag changes
     int rc = hrt_synchronize(c, nullptr);
     if (rc != HRT_OK) return rc;
     HIPCHK(c, hipSetDevice(d.device_id));
@@ -3242,10 +3260,10 @@ try {
     }
     const int blocks = (int)((outLen + 255) / 256);
     HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
-    if (pp->mode == HRT_PRESENT_TAAU || reproject)
+    if (mode == HRT_PRESENT_TAAU || reproject)
     {
         TaaK k;
-        k.outColor = d.present_color; k.inColorLow = d.fb.color; k.inObjIdLow = d.fb.objectId;
+        k.outColor = d.present_color; k.inColorLow = lowColor; k.inObjIdLow = d.fb.objectId;
         k.historyColor = d.taa_hist_color; k.historyObjId = d.taa_hist_obj;
         k.outW = outW; k.outH = outH; k.inW = inW; k.inH = inH;
         k.feedback = pp->feedback <= 0.f ? 0.075f : pp->feedback;          // tunables of RTTaa.cs:77-79; "<= 0 selects the default" as the
@@ -3269,9 +3287,9 @@ try {
         d.taa_history_valid = true; d.taa_hist_cam = c->frame_cam;     // the camera the history now belongs to
     }
     else if (inW == outW && inH == outH)
-        hipLaunchKernelGGL(hrt_blit_kernel, dim3(blocks), dim3(256), 0, d.stream, (const int32_t*)d.fb.color, (long long)d.nPix, d.present_color, (long long)outLen);
+        hipLaunchKernelGGL(hrt_blit_kernel, dim3(blocks), dim3(256), 0, d.stream, lowColor, (long long)d.nPix, d.present_color, (long long)outLen);
     else
-        hipLaunchKernelGGL(hrt_bilinear_upsample_kernel, dim3(blocks), dim3(256), 0, d.stream, (const int32_t*)d.fb.color, inW, inH, d.present_color, outW, outH);
+        hipLaunchKernelGGL(hrt_bilinear_upsample_kernel, dim3(blocks), dim3(256), 0, d.stream, lowColor, inW, inH, d.present_color, outW, outH);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
     if (out_color_host) HIPCHK(c, hipMemcpyAsync(out_color_host, d.present_color, outLen * 4, hipMemcpyDeviceToHost, d.stream));
@@ -3352,6 +3370,78 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_motion_vectors"); }
+
+int hrt_denoise(hrt_ctx* c, const hrt_denoise_params* dp, hrt_float3* out_radiance_host, int32_t* out_color_host, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (!dp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: params is NULL");
+    if (dp->iterations < 0 || dp->iterations > 8) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: iterations must be 1..8 (0 selects 5)");
+    if (dp->flags & ~(uint32_t)HRT_DENOISE_NO_DEMODULATE) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: unknown flag bit");
+    const int nd = (int)c->dev.size();
+    DeviceState& d = c->dev[0];
+    if (d.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise: no frame rendered yet");
+    if (d.strip_n != nd || d.row_begin != 0 || d.row_end != c->height) return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise: the last frame was a partial tile");
+    int rc = hrt_synchronize(c, nullptr);
+    if (rc != HRT_OK) return rc;
+    HIPCHK(c, hipSetDevice(d.device_id));
+    const int W = c->width;
+    for (int i = 1; i < nd; i++)
+    {   // everything on slot 0: bring the other slots' strips of what the filter reads over, as hrt_present brings colour
+        DeviceState& srcd = c->dev[(size_t)i];
+        if ((rc = copy_strips(c, srcd, d.fb.radiance, (const hrt_float3*)srcd.fb.radiance, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if ((rc = copy_strips(c, srcd, d.gb.normalWS, (const hrt_float3*)srcd.gb.normalWS, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if ((rc = copy_strips(c, srcd, d.gb.worldPos, (const hrt_float3*)srcd.gb.worldPos, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if ((rc = copy_strips(c, srcd, d.gb.baseColor, (const hrt_float3*)srcd.gb.baseColor, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if ((rc = copy_strips(c, srcd, d.fb.depth, (const float*)srcd.fb.depth, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+        if ((rc = copy_strips(c, srcd, d.gb.hitMask, (const int32_t*)srcd.gb.hitMask, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
+    }
+    HIPCHK(c, hipSetDevice(d.device_id));
+    const size_t nPix = (size_t)d.nPix;
+    if (d.dn_pix != d.nPix)
+    {   // a new frame size: new planes (the old pointers of hrt_denoised_buffers end here)
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        d.dn_mem.release(); d.dn_pix = 0; d.dn_radiance = nullptr; d.dn_color = nullptr; c->dn_serial = 0;
+        if ((rc = d.dn_mem.grow(c, nPix * 80, d.stream)) != HRT_OK) return rc;
+        d.dn_pix = d.nPix;
+        d.dn_radiance = (hrt_float3*)((char*)d.dn_mem.p + nPix * 64);
+        d.dn_color = (int32_t*)((char*)d.dn_mem.p + nPix * 76);
+    }
+    DenoiseLaunch L;
+    L.width = W; L.height = c->height;
+    L.iterations = dp->iterations == 0 ? 5 : dp->iterations;
+    L.demodulate = (dp->flags & HRT_DENOISE_NO_DEMODULATE) == 0;
+    const float sn = dp->sigma_normal <= 0.f ? 0.5f : dp->sigma_normal, sp = dp->sigma_plane <= 0.f ? 0.02f : dp->sigma_plane;     // "<= 0 selects the
+    L.sigma_color = dp->sigma_color <= 0.f ? 4.0f : dp->sigma_color;                                                              // default": a NaN goes through
+    L.kn = 1.0f / (sn * sn); L.sp2 = sp * sp;
+    L.radiance = d.fb.radiance; L.normalWS = d.gb.normalWS; L.worldPos = d.gb.worldPos; L.baseColor = d.gb.baseColor;
+    L.depth = d.fb.depth; L.hitMask = d.gb.hitMask;
+    L.guide = (float4*)d.dn_mem.p;
+    L.colour[0] = (float4*)((char*)d.dn_mem.p + nPix * 32); L.colour[1] = (float4*)((char*)d.dn_mem.p + nPix * 48);
+    L.outRadiance = d.dn_radiance; L.outColor = d.dn_color;
+    c->dn_serial = 0;                          // until the kernels are enqueued
+    HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
+    HIPCHK(c, denoise_launch(L, d.stream));
+    HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
+    if (out_radiance_host) HIPCHK(c, hipMemcpyAsync(out_radiance_host, d.dn_radiance, nPix * sizeof(hrt_float3), hipMemcpyDeviceToHost, d.stream));
+    if (out_color_host) HIPCHK(c, hipMemcpyAsync(out_color_host, d.dn_color, nPix * 4, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, d.q_ev[0], d.q_ev[1]));
+    if (device_ms) *device_ms = ms;
+    c->dn_serial = c->frame_serial;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_denoise"); }
+
+int hrt_denoised_buffers(hrt_ctx* c, void** radiance, void** color)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (radiance) *radiance = c->dev[0].dn_radiance;
+    if (color) *color = c->dev[0].dn_color;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_denoised_buffers"); }
 
 int hrt_set_workspace_limit(hrt_ctx* c, int64_t max_resident_paths)
 try {

@@ -61,6 +61,8 @@ def _load(path, hooks=False):
     L.hrt_present.argtypes = [C.c_void_p, C.POINTER(T.PresentParams), C.c_void_p]
     L.hrt_present_time.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.hrt_motion_vectors.argtypes = [C.c_void_p, C.POINTER(T.Camera), C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+    L.hrt_denoise.argtypes = [C.c_void_p, C.POINTER(T.DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.hrt_denoised_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.hrt_device_buffers.argtypes = [C.c_void_p, C.c_int, C.POINTER(T.DeviceViews)]
     L.hrt_reset_history.argtypes = [C.c_void_p]
     L.hrt_frame_times.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -622,13 +624,17 @@ class RTRenderer(FrameHost):
         """Caps the streamed pipeline's path workspace (0 = default): larger frames run in sample batches, same results."""
         self._check(self._L.hrt_set_workspace_limit(self._ctx, int(max_resident_paths)))
 
-    def present(self, out_width, out_height, taau=True, out=None, feedback=0.0, sharpness=0.0, clamp_k=0.0, reproject=False):
+    def present(self, out_width, out_height, taau=True, out=None, feedback=0.0, sharpness=0.0, clamp_k=0.0, reproject=False, denoised=False):
         """Presentation step of RenderDirectToPbo (RTRenderer.cs:208-231): TAAU resolve, or blit / bilinear upsample.
         reproject (with taau): the history is read where the camera's motion since the last resolved frame puts it
-        (HRT_PRESENT_TAAU_REPROJECT, include/hip_raytrace.h).  Returns the display-size packed colour as an int32 array."""
+        (HRT_PRESENT_TAAU_REPROJECT, include/hip_raytrace.h).  denoised: resolve the denoised colour of the last denoise() instead of
+        the frame's (HRT_PRESENT_DENOISED; an HrtError if the frame is newer than it).  Returns the display-size packed colour as an
+        int32 array."""
         if reproject and not taau:
             raise ValueError("reproject is a mode of the TAAU resolve (taau=True)")
         mode = T.PRESENT_TAAU_REPROJECT if reproject else (T.PRESENT_TAAU if taau else T.PRESENT_RESAMPLE)
+        if denoised:
+            mode |= T.PRESENT_DENOISED
         pp = T.PresentParams(out_width, out_height, mode, feedback, sharpness, clamp_k)
         if out is None:
             out = np.zeros(out_width * out_height, np.int32)
@@ -676,6 +682,32 @@ class RTRenderer(FrameHost):
             self._check(self._L.hrt_motion_vectors(self._ctx, cam, out.data_ptr(), 0, C.byref(ms)))
         self.last_query_ms = ms.value
         return out
+
+    def denoise(self, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_plane=0.0, demodulate=True, slot=None):
+        """Edge-avoiding a-trous filter over the radiance of the last full-image frame, guided by its G-buffer (hrt_denoise,
+        include/hip_raytrace.h).  iterations 1..8 (0: 5), iteration i with tap step 1 << i; sigmas <= 0 select 4.0 / 0.5 / 0.02;
+        demodulate=False filters the radiance itself instead of radiance / albedo.  The frame is left as it is; present(...,
+        denoised=True) shows the result.  slot=None: returns (radiance (h, w, 3) float32, color (h, w) int32) as numpy arrays.
+        slot=0: torch tensors of those shapes over the library's own device planes, no copy: valid until a denoise() at another
+        frame size or close(), overwritten by the next denoise()."""
+        v = self.device_views(0)
+        w, h = v.width, v.height
+        dp = T.DenoiseParams(int(iterations), 0 if demodulate else T.DENOISE_NO_DEMODULATE, sigma_color, sigma_normal, sigma_plane)
+        ms = C.c_float(0.0)
+        if slot is None:
+            rad, col = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.int32)
+            self._check(self._L.hrt_denoise(self._ctx, C.byref(dp), rad.ctypes.data, col.ctypes.data, C.byref(ms)))
+            self.last_query_ms = ms.value
+            return rad, col
+        if slot != 0:
+            raise ValueError("the denoised planes live on the device of slot 0 only (slot=0), or come to the host (slot=None)")
+        import torch                                       # lazy: the host path needs no torch
+        self._check(self._L.hrt_denoise(self._ctx, C.byref(dp), None, None, C.byref(ms)))
+        self.last_query_ms = ms.value
+        pr, pc = C.c_void_p(), C.c_void_p()
+        self._check(self._L.hrt_denoised_buffers(self._ctx, C.byref(pr), C.byref(pc)))
+        dev = "cuda:%d" % self.device_ids[0]
+        return (_device_plane(torch, pr.value, (h, w, 3), "<f4", dev, self), _device_plane(torch, pc.value, (h, w), "<i4", dev, self))
 
     def reset_history(self):
         self._check(self._L.hrt_reset_history(self._ctx))
@@ -881,6 +913,18 @@ _QUERIES = {"closest": T.QUERY_CLOSEST, "occluded": T.QUERY_OCCLUDED}
 
 _PROGRESSIVE_FORBIDDEN = {T.FLAG_COUNTERS: "FLAG_COUNTERS", T.FLAG_PRIMARY_ONLY: "FLAG_PRIMARY_ONLY",
                           T.FLAG_SKIP_PRIMARY: "FLAG_SKIP_PRIMARY", T.FLAG_EXCHANGED: "FLAG_EXCHANGED"}
+
+
+class _DevicePlane:
+    """A device plane of the library through __cuda_array_interface__; keeps its renderer alive."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def _device_plane(torch, ptr, shape, typestr, device, owner):
+    return torch.as_tensor(_DevicePlane(ptr, shape, typestr, owner), device=device)
 
 
 def _progressive_args(spp, sample_begin, flags, outputs):

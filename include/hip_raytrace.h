@@ -38,6 +38,8 @@
  *                                                                SceneDeviceViews.cs:30-237
  *   hrt_trace_paths        PathTraceKernel over caller rays in place of camera rays
  *                                                                RTRay.cs:187-199,203-325
+ *   hrt_denoise            nothing: the reference shows its 2 spp frame (RTRenderer.cs:43-49) through TAAU alone.  An edge-avoiding
+ *                          a-trous filter over the frame's radiance, guided by its G-buffer
  *   hrt_destroy            RTRenderer.Dispose                    RTRenderer.cs:347-363
  *   hrt_last_error         the exception message of CudaException / Argument*Exception
  *
@@ -434,6 +436,51 @@ int  hrt_trace_paths(hrt_ctx* ctx, const hrt_frame_params* params, uint32_t flag
                      const hrt_ray* rays, int64_t n, int64_t first_key,
                      hrt_path_result* results, int32_t dev, float* device_ms);
 int  hrt_reset_history(hrt_ctx* ctx);           /* zero both reservoir sets */
+
+/* ---- spatial denoiser: an edge-avoiding a-trous filter over the radiance of the last full-image frame, guided by its G-buffer.
+ * The filter, float32 under hrt_math.h, no contraction, statement order as written.  W, H = the frame's size, idx = y * W + x,
+ * dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z left to right, n = gb_normalWS, P = gb_worldPos:
+ *   1. Prepare, per pixel: hit = gb_hitMask[idx] != 0.  a = (1, 1, 1) when HRT_DENOISE_NO_DEMODULATE is set or !hit, else per channel
+ *      hrt_fmax(gb_baseColor, 0.01f).  c = radiance / a per channel (IEEE divide).
+ *      kx = 1.0f / (sigma_plane * sigma_plane * hrt_fmax(depth * depth, 1e-12f)).  Uniform: kn = 1.0f / (sigma_normal * sigma_normal).
+ *   2. Iteration i = 0 .. iterations-1: s = 1 << i, sc = sigma_color * 2^-i (exact), kc = 1.0f / (sc * sc).  It reads the plane
+ *      iteration i-1 wrote and writes another.  A pixel with !hit is copied.  For a hit pixel p, taps dy = -2..2 outer, dx = -2..2
+ *      inner, q = (x + dx*s, y + dy*s):
+ *        - skipped if q is outside the image or q is not a hit;
+ *        - dn = dot(n_p - n_q, n_p - n_q); d = dot(P_q - P_p, n_p); dc = dot(c_p - c_q, c_p - c_q);
+ *        - e = dn * kn + d * d * kx + dc * kc (kx of p); w = (h[dx] * h[dy]) * hrt_exp(-e), h = (1/16, 1/4, 3/8, 1/4, 1/16);
+ *        - skipped unless w > 0.0f (a NaN fails); else per channel acc += w * c_q (multiply, then add) and ws += w;
+ *      result: ws > 0.0f ? acc / ws : c_p per channel (IEEE divide).  A pixel whose own guides are NaN keeps its value.
+ *   3. Finish: out = c * a per channel -> the denoised radiance; pack_rgba8(out) (RTRay.cs:66-76, as the frame packs) -> the
+ *      denoised colour.
+ * Misses (sky) are noise-free and stay bit-equal to the frame's radiance.  Samples are SafeColor-clamped to +-1e6, so every c is
+ * finite; hostile guides (NaN / infinite normals or positions) fall to the w > 0 rule.
+ *   - Works on the last full-image frame (hrt_render_frame, or any call of hrt_render_progressive: a preview may be denoised between
+ *     refinements).  No frame yet, or a partial tile: HRT_ERR_INVALID_STATE, as hrt_present.
+ *   - Blocking; runs on device slot 0 after any HRT_FLAG_NO_SYNC frames.  A multi-device ctx first brings the other slots' strips of
+ *     radiance, normalWS, worldPos, baseColor, depth and hitMask to slot 0, as hrt_present brings colour.
+ *   - Writes two private planes on slot 0 (denoised radiance, float3; denoised colour, packed 0xFFRRGGBB) and works in a private
+ *     workspace (80 bytes per pixel in all), allocated on first use, re-allocated for a new frame size, freed by hrt_destroy.  Frame
+ *     state is untouched: radiance, colour, G-buffer, reservoirs, present history, hrt_frame_times, a pending progressive frame.
+ *   - out_radiance_host / out_color_host (either may be NULL): width * height elements, row 0 = bottom row as hrt_outputs.
+ *   - device_ms (may be NULL): HIP-event time of the denoise kernels alone (no strip or host copies).
+ *   - HRT_ERR_INVALID_ARG: NULL params, iterations < 0 or > 8, an unknown flag bit.
+ * The denoised planes belong to the frame they were made from: hrt_present with HRT_PRESENT_DENOISED in its mode resolves the
+ * denoised colour in place of the frame's (modes 0, 1 and 2 otherwise unchanged: objectId and gb_worldPos stay the frame's), and
+ * returns HRT_ERR_INVALID_STATE after a newer frame, scene upload or resize until hrt_denoise has run again.
+ * Out of scope: temporal accumulation of radiance, variance estimation, denoising at display resolution, object motion. */
+enum hrt_denoise_flags { HRT_DENOISE_NO_DEMODULATE = 1u << 0 };
+typedef struct hrt_denoise_params {
+    int32_t  iterations;      /* 1..8; 0 selects 5.  Iteration i uses tap step 1 << i                         */
+    uint32_t flags;           /* hrt_denoise_flags; any other bit: HRT_ERR_INVALID_ARG                        */
+    float    sigma_color, sigma_normal, sigma_plane;   /* <= 0 selects 4.0, 0.5, 0.02; a NaN goes through, as in hrt_present */
+} hrt_denoise_params;
+int  hrt_denoise(hrt_ctx* ctx, const hrt_denoise_params* params, hrt_float3* out_radiance_host /* may be NULL */,
+                 int32_t* out_color_host /* may be NULL */, float* device_ms /* may be NULL */);
+/* slot 0 device pointers of the denoised radiance (hrt_float3) and colour (int32) planes; NULL before the first hrt_denoise.  Valid
+ * until an hrt_denoise at another frame size, or hrt_destroy. */
+int  hrt_denoised_buffers(hrt_ctx* ctx, void** radiance, void** color);
+#define HRT_PRESENT_DENOISED 0x100   /* OR into hrt_present_params.mode: resolve the denoised colour instead of the frame's */
 
 /* Test hooks (math probes, host-side builders of derived trees) are declared in hrt_test_hooks.h and exist only in
  * libhip_raytrace_test.so, the -DHRT_TEST_HOOKS build of the same sources; the shipped library exports none of them. */
