@@ -84,6 +84,20 @@ namespace ILGPU_Raytracing.Engine
             return ms;
         }
 
+        /// <summary>The temporal denoiser (hrt_denoise_temporal): accumulates the demodulated radiance and its luminance moments of the last
+        /// full-image frame into a history reprojected with the camera's motion, then filters with a-trous passes guided by the per-pixel
+        /// variance.  Call it once per frame; Present(..., denoised: true) resolves the result.  p null: every default.  Returns the
+        /// HIP-event time of the kernels in ms.</summary>
+        public float DenoiseTemporal(Span<Float3> radiance = default, Span<int> color = default, HrtDenoiseTemporalParams? p = null)
+        {
+            var tp = p ?? default;
+            float ms = 0f;
+            fixed (Float3* r = radiance)
+            fixed (int* c = color)
+                HipRaytrace.Check(_ctx, HipRaytrace.hrt_denoise_temporal(_ctx, &tp, radiance.IsEmpty ? null : r, color.IsEmpty ? null : c, &ms));
+            return ms;
+        }
+
         /// <summary>Camera motion vectors of the last full-image frame (hrt_motion_vectors), one per internal pixel, in pixels: where the
         /// pixel's surface point was in fromCam's image minus where it is now; NaN where the point is behind either camera.
         /// fromCam null: the frame's prevCam.</summary>

@@ -56,6 +56,18 @@ namespace ILGPU_Raytracing.Engine
     [StructLayout(LayoutKind.Sequential)]
     public struct HrtDenoiseParams { public int iterations; public uint flags; public float sigma_color, sigma_normal, sigma_plane; }
     [Flags] public enum HrtDenoiseFlags : uint { None = 0, NoDemodulate = 1 }
+    // hrt_denoise_temporal_params: values <= 0 select the defaults of include/hip_raytrace.h
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtDenoiseTemporalParams
+    {
+        public int iterations; public uint flags;
+        public float alpha_color, alpha_moments, sigma_lum, sigma_normal, sigma_plane, normal_cos_min, plane_tol;
+        public int max_history;
+    }
+    [Flags] public enum HrtDenoiseTemporalFlags : uint { None = 0, NoDemodulate = 1, NoSpatial = 2, Reset = 4 }
+    // hrt_denoise_history_views: slot 0 device pointers of the temporal denoiser's history, records of `stride` floats per pixel
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HrtDenoiseHistoryViews { public IntPtr color, moments, length, variance; public int width, height, stride, reserved; }
 
     [StructLayout(LayoutKind.Sequential)]
     public unsafe struct HrtOutputs               // host destinations of one frame, any may be null
@@ -134,6 +146,10 @@ namespace ILGPU_Raytracing.Engine
         // a-trous denoiser over the last full-image frame; either host destination may be null (the planes stay on device slot 0)
         [DllImport(Lib)] public static extern int hrt_denoise(IntPtr ctx, HrtDenoiseParams* p, Float3* outRadianceHost, int* outColorHost, float* deviceMs);
         [DllImport(Lib)] public static extern int hrt_denoised_buffers(IntPtr ctx, IntPtr* radiance, IntPtr* color);
+        // the temporal, variance-guided denoiser: one call per frame, the same result planes as hrt_denoise
+        [DllImport(Lib)] public static extern int hrt_denoise_temporal(IntPtr ctx, HrtDenoiseTemporalParams* p, Float3* outRadianceHost, int* outColorHost, float* deviceMs);
+        [DllImport(Lib)] public static extern int hrt_denoise_history(IntPtr ctx, HrtDenoiseHistoryViews* views);
+        [DllImport(Lib)] public static extern int hrt_denoise_history_read(IntPtr ctx, float* colorHost, float* momentsHost);   // 4 floats per pixel each, either may be null
         // camera motion vectors of the last full-image frame, in pixels; fromCam null: the frame's prevCam; dev < 0 host memory, 0 device memory of slot 0
         [DllImport(Lib)] public static extern int hrt_motion_vectors(IntPtr ctx, Camera* fromCam, Float2* mv, int dev, float* deviceMs);
         [DllImport(Lib)] public static extern int hrt_synchronize(IntPtr ctx, HrtStats* stats);

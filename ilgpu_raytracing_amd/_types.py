@@ -174,6 +174,21 @@ class DenoiseParams(C.Structure):     # hrt_denoise_params
 DENOISE_NO_DEMODULATE = 1             # hrt_denoise_flags
 
 
+class DenoiseTemporalParams(C.Structure):     # hrt_denoise_temporal_params
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32),
+                ("alpha_color", C.c_float), ("alpha_moments", C.c_float),
+                ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("normal_cos_min", C.c_float), ("plane_tol", C.c_float), ("max_history", C.c_int32)]
+
+
+DENOISE_T_NO_DEMODULATE, DENOISE_T_NO_SPATIAL, DENOISE_T_RESET = 1, 2, 4      # hrt_denoise_temporal_flags
+
+
+class DenoiseHistoryViews(C.Structure):       # hrt_denoise_history_views
+    _fields_ = [(n, C.c_void_p) for n in ("color", "moments", "length", "variance")] + \
+               [(n, C.c_int32) for n in ("width", "height", "stride", "reserved")]
+
+
 class Ray(C.Structure):               # hrt_ray: a ray of hrt_trace_rays
     _fields_ = [("origin", Float3), ("tMax", C.c_float), ("dir", Float3), ("pad", C.c_float)]
 

@@ -29,6 +29,7 @@
 #include "hrt_paths.hpp"
 #include "hrt_hits.hpp"
 #include "hrt_denoise.hpp"
+#include "hrt_denoise_temporal.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
 #include "../../include/hrt_test_hooks.h"
@@ -611,6 +612,13 @@ struct DeviceState {
     int64_t dn_pix = 0;
     hrt_float3* dn_radiance = nullptr;
     int32_t* dn_color = nullptr;
+    // hrt_denoise_temporal, device slot 0 only: two guide sets (32 B per pixel each), two history colour and two history moment planes
+    // (16 B each); set dt_cur holds what the last call wrote.  dt_valid: the history is not empty; dt_cam: the camera of the frame it
+    // was last accumulated from (what the next call reprojects from)
+    Scratch dt_mem;
+    int dt_w = 0, dt_h = 0, dt_cur = 0;
+    bool dt_valid = false;
+    hrt_camera dt_cam{};
 };
 
 } // namespace
@@ -639,7 +647,8 @@ struct hrt_ctx {
     int width = 0, height = 0;
     hrt_camera frame_cam{}, frame_prev_cam{};  // cam / prevCam of the last frame call (what gb_worldPos was rendered from)
     uint64_t frame_serial = 0;                 // counts frame calls and scene uploads: what the denoised planes are checked against
-    uint64_t dn_serial = 0;                    // frame_serial of the frame hrt_denoise last ran on (0: never)
+    uint64_t dn_serial = 0;                    // frame_serial of the frame hrt_denoise or hrt_denoise_temporal last ran on (0: never)
+    uint64_t dt_serial = 0;                    // frame_serial of the frame hrt_denoise_temporal last accumulated (0: never)
     long long max_resident_paths = 0;          // hrt_set_workspace_limit: 0 = kWfMaxPaths
     std::vector<std::pair<char*, size_t>> pinned;   // hrt_host_register: page-locked ranges of the caller (gather targets)
     // the progressive frame a continuation (hrt_render_progressive with sample_begin > 0) may extend: what its last call rendered.
@@ -1679,6 +1688,7 @@ void free_query(DeviceState& d)
     d.q_pin.release(true);
     d.mv_mem.release();
     d.dn_mem.release(); d.dn_pix = 0; d.dn_radiance = nullptr; d.dn_color = nullptr;
+    d.dt_mem.release(); d.dt_w = d.dt_h = 0; d.dt_valid = false;
     for (hipEvent_t& e : d.q_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
 }
 
@@ -2065,6 +2075,7 @@ try {
     if (!c) return HRT_ERR_INVALID_ARG;
     c->prog.valid = false;                     // a progressive frame cannot be continued across this call
     c->frame_serial++;                         // ... and denoised planes no longer belong to what is on the device
+    c->dev[0].dt_valid = false;                // ... nor does the temporal denoiser's history
     if (!s) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: scene is NULL");
     const void* src[15] = {s->tlasNodes, s->tlasInstanceIndices, s->instances, s->blasNodes, s->spherePrimIdx, s->spheres,
                            s->triPrimIdx, s->meshPositions, s->meshTris, s->meshTexcoords, s->meshTriUVs, s->triMatIndex,
@@ -2891,6 +2902,7 @@ try {
     for (DeviceState& d : c->dev)
     {
         d.taa_history_valid = false;
+        d.dt_valid = false;
         if (d.nPix == 0) continue;
         HIPCHK(c, hipSetDevice(d.device_id));
         DReservoir* rs[2] = {&d.resA, &d.resB};
@@ -3371,23 +3383,29 @@ try {
 }
 catch (...) { return on_exception(c, "hrt_motion_vectors"); }
 
-int hrt_denoise(hrt_ctx* c, const hrt_denoise_params* dp, hrt_float3* out_radiance_host, int32_t* out_color_host, float* device_ms)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    if (device_ms) *device_ms = 0.f;
-    if (!dp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: params is NULL");
-    if (dp->iterations < 0 || dp->iterations > 8) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: iterations must be 1..8 (0 selects 5)");
-    if (dp->flags & ~(uint32_t)HRT_DENOISE_NO_DEMODULATE) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: unknown flag bit");
+namespace {
+
+// what both denoisers do before their kernels: the frame checks, then everything on slot 0 (the other slots' strips of what the
+// filters read are brought over, as hrt_present brings colour) and the workspace with the two result planes
+int denoise_frame_check(hrt_ctx* c, const char* who)
+{
     const int nd = (int)c->dev.size();
     DeviceState& d = c->dev[0];
-    if (d.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise: no frame rendered yet");
-    if (d.strip_n != nd || d.row_begin != 0 || d.row_end != c->height) return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise: the last frame was a partial tile");
+    if (d.nPix == 0 || c->width <= 0) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": no frame rendered yet");
+    if (d.strip_n != nd || d.row_begin != 0 || d.row_end != c->height) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": the last frame was a partial tile");
+    return HRT_OK;
+}
+
+int denoise_gather(hrt_ctx* c)
+{
+    const int nd = (int)c->dev.size();
+    DeviceState& d = c->dev[0];
     int rc = hrt_synchronize(c, nullptr);
     if (rc != HRT_OK) return rc;
     HIPCHK(c, hipSetDevice(d.device_id));
     const int W = c->width;
     for (int i = 1; i < nd; i++)
-    {   // everything on slot 0: bring the other slots' strips of what the filter reads over, as hrt_present brings colour
+    {
         DeviceState& srcd = c->dev[(size_t)i];
         if ((rc = copy_strips(c, srcd, d.fb.radiance, (const hrt_float3*)srcd.fb.radiance, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
         if ((rc = copy_strips(c, srcd, d.gb.normalWS, (const hrt_float3*)srcd.gb.normalWS, W, hipMemcpyDeviceToDevice, d.stream)) != HRT_OK) return rc;
@@ -3407,8 +3425,40 @@ try {
         d.dn_radiance = (hrt_float3*)((char*)d.dn_mem.p + nPix * 64);
         d.dn_color = (int32_t*)((char*)d.dn_mem.p + nPix * 76);
     }
+    return HRT_OK;
+}
+
+// after the kernels were enqueued between q_ev[0] and q_ev[1]: the host copies, the wait and the time
+int denoise_finish(hrt_ctx* c, hrt_float3* out_radiance_host, int32_t* out_color_host, float* device_ms)
+{
+    DeviceState& d = c->dev[0];
+    const size_t nPix = (size_t)d.nPix;
+    if (out_radiance_host) HIPCHK(c, hipMemcpyAsync(out_radiance_host, d.dn_radiance, nPix * sizeof(hrt_float3), hipMemcpyDeviceToHost, d.stream));
+    if (out_color_host) HIPCHK(c, hipMemcpyAsync(out_color_host, d.dn_color, nPix * 4, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, d.q_ev[0], d.q_ev[1]));
+    if (device_ms) *device_ms = ms;
+    c->dn_serial = c->frame_serial;
+    return HRT_OK;
+}
+
+} // namespace
+
+int hrt_denoise(hrt_ctx* c, const hrt_denoise_params* dp, hrt_float3* out_radiance_host, int32_t* out_color_host, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (!dp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: params is NULL");
+    if (dp->iterations < 0 || dp->iterations > 8) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: iterations must be 1..8 (0 selects 5)");
+    if (dp->flags & ~(uint32_t)HRT_DENOISE_NO_DEMODULATE) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise: unknown flag bit");
+    int rc = denoise_frame_check(c, "hrt_denoise");
+    if (rc != HRT_OK) return rc;
+    if ((rc = denoise_gather(c)) != HRT_OK) return rc;
+    DeviceState& d = c->dev[0];
+    const size_t nPix = (size_t)d.nPix;
     DenoiseLaunch L;
-    L.width = W; L.height = c->height;
+    L.width = c->width; L.height = c->height;
     L.iterations = dp->iterations == 0 ? 5 : dp->iterations;
     L.demodulate = (dp->flags & HRT_DENOISE_NO_DEMODULATE) == 0;
     const float sn = dp->sigma_normal <= 0.f ? 0.5f : dp->sigma_normal, sp = dp->sigma_plane <= 0.f ? 0.02f : dp->sigma_plane;     // "<= 0 selects the
@@ -3423,16 +3473,103 @@ try {
     HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
     HIPCHK(c, denoise_launch(L, d.stream));
     HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
-    if (out_radiance_host) HIPCHK(c, hipMemcpyAsync(out_radiance_host, d.dn_radiance, nPix * sizeof(hrt_float3), hipMemcpyDeviceToHost, d.stream));
-    if (out_color_host) HIPCHK(c, hipMemcpyAsync(out_color_host, d.dn_color, nPix * 4, hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, d.q_ev[0], d.q_ev[1]));
-    if (device_ms) *device_ms = ms;
-    c->dn_serial = c->frame_serial;
-    return HRT_OK;
+    return denoise_finish(c, out_radiance_host, out_color_host, device_ms);
 }
 catch (...) { return on_exception(c, "hrt_denoise"); }
+
+int hrt_denoise_temporal(hrt_ctx* c, const hrt_denoise_temporal_params* tp, hrt_float3* out_radiance_host, int32_t* out_color_host, float* device_ms)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    if (device_ms) *device_ms = 0.f;
+    if (!tp) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise_temporal: params is NULL");
+    if (tp->iterations < 0 || tp->iterations > 8) return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise_temporal: iterations must be 1..8 (0 selects 5)");
+    if (tp->flags & ~(uint32_t)(HRT_DENOISE_T_NO_DEMODULATE | HRT_DENOISE_T_NO_SPATIAL | HRT_DENOISE_T_RESET))
+        return fail(c, HRT_ERR_INVALID_ARG, "hrt_denoise_temporal: unknown flag bit");
+    int rc = denoise_frame_check(c, "hrt_denoise_temporal");
+    if (rc != HRT_OK) return rc;
+    if (c->dt_serial == c->frame_serial)
+        return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise_temporal: this frame has already been accumulated into the history (one call per frame)");
+    if ((rc = denoise_gather(c)) != HRT_OK) return rc;
+    DeviceState& d = c->dev[0];
+    const size_t nPix = (size_t)d.nPix;
+    const int W = c->width, Hh = c->height;
+    if (d.dt_w != W || d.dt_h != Hh)
+    {   // a new frame size: a new, empty history
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        d.dt_mem.release(); d.dt_w = d.dt_h = 0; d.dt_valid = false;
+        if ((rc = d.dt_mem.grow(c, nPix * 128, d.stream)) != HRT_OK) return rc;
+        d.dt_w = W; d.dt_h = Hh; d.dt_cur = 0;
+    }
+    if (tp->flags & HRT_DENOISE_T_RESET) d.dt_valid = false;
+    const int prev = d.dt_cur, cur = prev ^ 1;
+    char* base = (char*)d.dt_mem.p;
+    auto guide = [&](int k) { return (float4*)(base + nPix * 32 * (size_t)k); };
+    auto hcol = [&](int k) { return (float4*)(base + nPix * 64 + nPix * 16 * (size_t)k); };
+    auto hmom = [&](int k) { return (float4*)(base + nPix * 96 + nPix * 16 * (size_t)k); };
+    DenoiseTemporalLaunch L;
+    L.width = W; L.height = Hh;
+    L.iterations = tp->iterations == 0 ? 5 : tp->iterations;
+    L.demodulate = (tp->flags & HRT_DENOISE_T_NO_DEMODULATE) == 0;
+    L.spatial = (tp->flags & HRT_DENOISE_T_NO_SPATIAL) == 0;
+    L.haveHistory = d.dt_valid;
+    const float sn = tp->sigma_normal <= 0.f ? 0.5f : tp->sigma_normal, sp = tp->sigma_plane <= 0.f ? 0.02f : tp->sigma_plane;     // "<= 0 selects the
+    L.sigma_lum = tp->sigma_lum <= 0.f ? 0.7f : tp->sigma_lum;                                                                    // default": a NaN goes through
+    L.kn = 1.0f / (sn * sn); L.sp2 = sp * sp;
+    const float ac = tp->alpha_color <= 0.f ? 0.2f : tp->alpha_color, am = tp->alpha_moments <= 0.f ? 0.2f : tp->alpha_moments;
+    L.alpha_color = ac > 1.0f ? 1.0f : ac; L.alpha_moments = am > 1.0f ? 1.0f : am;
+    L.normal_cos_min = tp->normal_cos_min <= 0.f ? 0.9f : tp->normal_cos_min;
+    L.plane_tol = tp->plane_tol <= 0.f ? 0.02f : tp->plane_tol;
+    L.max_history = (float)(tp->max_history <= 0 ? 64 : tp->max_history);
+    L.curCam = proj_cam(c->frame_cam);
+    L.histCam = proj_cam(d.dt_valid ? d.dt_cam : c->frame_cam);
+    L.radiance = d.fb.radiance; L.normalWS = d.gb.normalWS; L.worldPos = d.gb.worldPos; L.baseColor = d.gb.baseColor;
+    L.depth = d.fb.depth; L.hitMask = d.gb.hitMask;
+    L.guideCur = guide(cur); L.guidePrev = guide(prev);
+    L.hcolPrev = hcol(prev); L.hmomPrev = hmom(prev); L.hcolNew = hcol(cur); L.hmomNew = hmom(cur);
+    L.work[0] = (float4*)((char*)d.dn_mem.p + nPix * 32); L.work[1] = (float4*)((char*)d.dn_mem.p + nPix * 48);
+    L.outRadiance = d.dn_radiance; L.outColor = d.dn_color;
+    c->dn_serial = 0;                          // until the kernels are enqueued
+    d.dt_valid = false;                        // ... and the history is whole again
+    HIPCHK(c, hipEventRecord(d.q_ev[0], d.stream));
+    HIPCHK(c, denoise_temporal_launch(L, d.stream));
+    HIPCHK(c, hipEventRecord(d.q_ev[1], d.stream));
+    if ((rc = denoise_finish(c, out_radiance_host, out_color_host, device_ms)) != HRT_OK) return rc;
+    d.dt_cur = cur; d.dt_valid = true; d.dt_cam = c->frame_cam;
+    c->dt_serial = c->frame_serial;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_denoise_temporal"); }
+
+int hrt_denoise_history(hrt_ctx* c, hrt_denoise_history_views* out)
+try {
+    if (!c || !out) return HRT_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof(*out));
+    const DeviceState& d = c->dev[0];
+    if (!d.dt_valid) return HRT_OK;
+    const size_t nPix = (size_t)d.dt_w * (size_t)d.dt_h;
+    const char* base = (const char*)d.dt_mem.p;
+    out->color = (const float*)(base + nPix * 64 + nPix * 16 * (size_t)d.dt_cur);
+    out->moments = (const float*)(base + nPix * 96 + nPix * 16 * (size_t)d.dt_cur);
+    out->length = out->moments + 2; out->variance = out->color + 3;
+    out->width = d.dt_w; out->height = d.dt_h; out->stride = 4;
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_denoise_history"); }
+
+int hrt_denoise_history_read(hrt_ctx* c, float* color_host, float* moments_host)
+try {
+    if (!c) return HRT_ERR_INVALID_ARG;
+    DeviceState& d = c->dev[0];
+    if (!d.dt_valid) return fail(c, HRT_ERR_INVALID_STATE, "hrt_denoise_history_read: the history is empty");
+    const size_t bytes = (size_t)d.dt_w * (size_t)d.dt_h * 16;
+    const char* base = (const char*)d.dt_mem.p;
+    HIPCHK(c, hipSetDevice(d.device_id));
+    if (color_host) HIPCHK(c, hipMemcpyAsync(color_host, base + bytes * 4 + bytes * (size_t)d.dt_cur, bytes, hipMemcpyDeviceToHost, d.stream));
+    if (moments_host) HIPCHK(c, hipMemcpyAsync(moments_host, base + bytes * 6 + bytes * (size_t)d.dt_cur, bytes, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    return HRT_OK;
+}
+catch (...) { return on_exception(c, "hrt_denoise_history_read"); }
 
 int hrt_denoised_buffers(hrt_ctx* c, void** radiance, void** color)
 try {

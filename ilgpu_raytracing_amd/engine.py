@@ -63,6 +63,9 @@ def _load(path, hooks=False):
     L.hrt_motion_vectors.argtypes = [C.c_void_p, C.POINTER(T.Camera), C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
     L.hrt_denoise.argtypes = [C.c_void_p, C.POINTER(T.DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     L.hrt_denoised_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.hrt_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(T.DenoiseTemporalParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.hrt_denoise_history.argtypes = [C.c_void_p, C.POINTER(T.DenoiseHistoryViews)]
+    L.hrt_denoise_history_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.hrt_device_buffers.argtypes = [C.c_void_p, C.c_int, C.POINTER(T.DeviceViews)]
     L.hrt_reset_history.argtypes = [C.c_void_p]
     L.hrt_frame_times.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -708,6 +711,48 @@ class RTRenderer(FrameHost):
         self._check(self._L.hrt_denoised_buffers(self._ctx, C.byref(pr), C.byref(pc)))
         dev = "cuda:%d" % self.device_ids[0]
         return (_device_plane(torch, pr.value, (h, w, 3), "<f4", dev, self), _device_plane(torch, pc.value, (h, w), "<i4", dev, self))
+
+    def denoise_temporal(self, iterations=0, alpha_color=0.0, alpha_moments=0.0, sigma_lum=0.0, sigma_normal=0.0, sigma_plane=0.0,
+                         normal_cos_min=0.0, plane_tol=0.0, max_history=0, demodulate=True, spatial=True, reset=False, slot=None):
+        """The temporal denoiser (hrt_denoise_temporal, include/hip_raytrace.h): accumulates the demodulated radiance and its luminance
+        moments of the last full-image frame into a reprojected history, then runs a-trous passes whose colour term follows the
+        per-pixel variance.  One call per frame; arguments of 0 select the defaults.  spatial=False: plain temporal accumulation;
+        reset=True: start from an empty history.  Returns what denoise() returns, in the same planes: present(..., denoised=True) shows
+        whichever of the two ran last on the frame."""
+        v = self.device_views(0)
+        w, h = v.width, v.height
+        flags = (0 if demodulate else T.DENOISE_T_NO_DEMODULATE) | (0 if spatial else T.DENOISE_T_NO_SPATIAL) | (T.DENOISE_T_RESET if reset else 0)
+        tp = T.DenoiseTemporalParams(int(iterations), flags, alpha_color, alpha_moments, sigma_lum, sigma_normal, sigma_plane,
+                                     normal_cos_min, plane_tol, int(max_history))
+        ms = C.c_float(0.0)
+        if slot is None:
+            rad, col = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.int32)
+            self._check(self._L.hrt_denoise_temporal(self._ctx, C.byref(tp), rad.ctypes.data, col.ctypes.data, C.byref(ms)))
+            self.last_query_ms = ms.value
+            return rad, col
+        if slot != 0:
+            raise ValueError("the denoised planes live on the device of slot 0 only (slot=0), or come to the host (slot=None)")
+        import torch                                       # lazy: the host path needs no torch
+        self._check(self._L.hrt_denoise_temporal(self._ctx, C.byref(tp), None, None, C.byref(ms)))
+        self.last_query_ms = ms.value
+        pr, pc = C.c_void_p(), C.c_void_p()
+        self._check(self._L.hrt_denoised_buffers(self._ctx, C.byref(pr), C.byref(pc)))
+        dev = "cuda:%d" % self.device_ids[0]
+        return (_device_plane(torch, pr.value, (h, w, 3), "<f4", dev, self), _device_plane(torch, pc.value, (h, w), "<i4", dev, self))
+
+    def denoise_history(self):
+        """The temporal denoiser's current history, copied to the host (hrt_denoise_history_read): dict of color (h, w, 3), variance,
+        length (h, w) and moments (h, w, 2) float32 arrays, or None while the history is empty."""
+        hv = T.DenoiseHistoryViews()
+        self._check(self._L.hrt_denoise_history(self._ctx, C.byref(hv)))
+        if not hv.color:
+            return None
+        n = hv.width * hv.height
+        col, mom = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+        self._check(self._L.hrt_denoise_history_read(self._ctx, col.ctypes.data, mom.ctypes.data))
+        shape = (hv.height, hv.width)
+        return dict(color=col[:, :3].reshape(shape + (3,)).copy(), variance=col[:, 3].reshape(shape).copy(),
+                    moments=mom[:, :2].reshape(shape + (2,)).copy(), length=mom[:, 2].reshape(shape).copy())
 
     def reset_history(self):
         self._check(self._L.hrt_reset_history(self._ctx))

@@ -468,7 +468,7 @@ int  hrt_reset_history(hrt_ctx* ctx);           /* zero both reservoir sets */
  * The denoised planes belong to the frame they were made from: hrt_present with HRT_PRESENT_DENOISED in its mode resolves the
  * denoised colour in place of the frame's (modes 0, 1 and 2 otherwise unchanged: objectId and gb_worldPos stay the frame's), and
  * returns HRT_ERR_INVALID_STATE after a newer frame, scene upload or resize until hrt_denoise has run again.
- * Out of scope: temporal accumulation of radiance, variance estimation, denoising at display resolution, object motion. */
+ * Out of scope: denoising at display resolution, object motion; temporal accumulation and variance guidance are hrt_denoise_temporal's. */
 enum hrt_denoise_flags { HRT_DENOISE_NO_DEMODULATE = 1u << 0 };
 typedef struct hrt_denoise_params {
     int32_t  iterations;      /* 1..8; 0 selects 5.  Iteration i uses tap step 1 << i                         */
@@ -481,6 +481,82 @@ int  hrt_denoise(hrt_ctx* ctx, const hrt_denoise_params* params, hrt_float3* out
  * until an hrt_denoise at another frame size, or hrt_destroy. */
 int  hrt_denoised_buffers(hrt_ctx* ctx, void** radiance, void** color);
 #define HRT_PRESENT_DENOISED 0x100   /* OR into hrt_present_params.mode: resolve the denoised colour instead of the frame's */
+
+/* ---- temporal denoiser: hrt_denoise's filter with the demodulated radiance and its luminance moments accumulated over frames (in
+ * float, at internal resolution, read where the camera's motion puts each surface point) and with the colour term of the a-trous
+ * passes driven by a per-pixel variance instead of a constant (SVGF-shaped).  It writes the same two result planes as hrt_denoise
+ * and stamps them with the frame: hrt_denoised_buffers and HRT_PRESENT_DENOISED serve whichever of the two ran last on the frame.
+ * float32 under hrt_math.h, no contraction, statement order as written.  W, H, idx, dot, n, P as for hrt_denoise;
+ * lum(v) = 0.2126f*v.x + 0.7152f*v.y + 0.0722f*v.z, left to right.  Parameters after their defaults; the host also replaces an
+ * alpha > 1 by 1 (a NaN goes through).  A "record" is four floats; history records are kept for the next call.
+ *   1. Prepare, per pixel: hit, a, c, kx, kn as steps 1 of hrt_denoise (HRT_DENOISE_T_NO_DEMODULATE for its flag).  The guide values
+ *      (n, kx, P, hit) are kept in one of two sets; the other set holds the previous call's: the geometry of the history.
+ *   2. Temporal, per pixel p = (px, py).  !hit: colour record (c, 0), moment record (0, 0, 0, 0).  hit:
+ *      - m = (okh && okc, hx - cx, hy - cy) of step 4 of HRT_PRESENT_TAAU_REPROJECT with P = P_p, outW, outH = W, H and for historyCam
+ *        the cam of the frame this entry point last accumulated (recorded on slot 0, never params.prevCam).  qx = (float)px + m.dx,
+ *        qy = (float)py + m.dy; valid = step 5 there, and false while the history is empty.
+ *      - hn = 0.  valid: x0 = floor(qx), fx = qx - x0, x1 = min(x0 + 1, W - 1), likewise y.  Taps t in the order (x0, y0), (x1, y0),
+ *        (x0, y1), (x1, y1) with weights wt = (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy.  A tap is accepted when wt > 0.0f, it was a hit
+ *        in the previous guides, dot(n_p, n_t) >= normal_cos_min and hrt_abs(dot(P_t - P_p, n_p)) <= plane_tol * depth_p (n_t, P_t from
+ *        the previous guides, depth_p the frame's depth; a NaN fails).  Accepted: ws += wt; hc += wt * C_t per channel, hm1 += wt * M1_t,
+ *        hm2 += wt * M2_t, hs += wt * N_t (multiply, then add; all start at 0; C_t, M1_t, M2_t, N_t = the history records of t).
+ *        ws > 0.0f: hc, hm1, hm2 are divided by ws and hn = hs / ws.
+ *      - l = lum(c).  !(hn > 0.0f) (no history): C = c, M1 = l, M2 = l * l, N = 1, taken as they are.  Else N = hrt_fmin(hn + 1.0f,
+ *        (float)max_history), r = 1.0f / N, ac = hrt_fmax(r, alpha_color), am = hrt_fmax(r, alpha_moments), C = hc + (c - hc) * ac per
+ *        channel, M1 = hm1 + (l - hm1) * am, M2 = hm2 + (l * l - hm2) * am.
+ *      - colour record (C, 0), moment record (M1, M2, N, 0).  The history is a pair of record planes each, swapped per call: a lane
+ *        reads records other lanes write.
+ *      A camera bitwise equal to the history camera gives fx = fy = 0: one tap of weight 1, and x * 1 / 1 is exact, so a static camera
+ *      reads its own pixel's history unresampled.
+ *   3. Variance v, the fourth word of the colour record (a kernel of its own).  !hit: 0.  N >= 4.0f: v = hrt_fmax(M2 - M1 * M1, 0.0f).
+ *      Else over the 7x7 window, dy = -3..3 outer, dx = -3..3 inner, q = (x + dx, y + dy) inside the image and a hit: dn, d as hrt_denoise,
+ *      w = hrt_exp(-(dn * kn + d * d * kx)); w > 0.0f: S1 += w * M1_q, S2 += w * M2_q, sw += w.  sw > 0.0f: S1 = S1 / sw, S2 = S2 / sw,
+ *      v = hrt_fmax(S2 - S1 * S1, 0.0f) * (4.0f / N); else the moment formula.
+ *   4. A-trous, iteration i = 0 .. iterations-1, s = 1 << i, on records (c, v); a pixel with !hit is copied.  Hit pixel p:
+ *      - vs = gs = 0; dy = -1..1 outer, dx = -1..1 inner, q = (x + dx*s, y + dy*s) inside the image and a hit: g = k[dx] * k[dy],
+ *        k = (1/4, 1/2, 1/4); vs += g * v_q; gs += g.  vf = vs / gs.  kl = 1.0f / (sigma_lum * hrt_sqrt(vf) + 1e-6f).  (The taps lie on
+ *        the step-s lattice, not on adjacent pixels: the one deviation from SVGF's prefilter.)
+ *      - the 25 taps of hrt_denoise step 2 with e = dn * kn + d * d * kx + hrt_abs(lum(c_p) - lum(c_q)) * kl and, where w > 0.0f,
+ *        acc += w * c_q, va += (w * w) * v_q, ws += w.  ws > 0.0f: c' = acc / ws per channel, v' = va / (ws * ws); else (c_p, v_p).
+ *      - iteration 0 also writes its (c', v') records (copies of misses included) to the history colour plane: what the next call sees.
+ *      - the last iteration finishes as hrt_denoise step 3.
+ *   5. HRT_DENOISE_T_NO_SPATIAL: steps 3 and 4 are skipped; out = C * a, the history colour record is (C, 0).
+ * Misses stay bit-equal to the frame's radiance.  On an empty history with NO_SPATIAL the output is (radiance / a) * a.
+ *   - Preconditions, blocking, slot 0, the strips of a multi-device ctx, out_*_host, device_ms: as hrt_denoise.
+ *   - HRT_ERR_INVALID_ARG: NULL params, iterations < 0 or > 8, an unknown flag bit.  HRT_ERR_INVALID_STATE: no frame yet, a partial
+ *     tile, or a frame this entry point has already accumulated (one call per frame serial; the refused call changes nothing).
+ *   - History: private to slot 0 (two guide sets, two colour and two moment record planes: 128 bytes per pixel beside
+ *     hrt_denoise's 80-byte workspace, whose colour and result planes it shares), allocated on first use, freed by hrt_destroy.  hrt_reset_history, hrt_scene_upload, a new frame size
+ *     and HRT_DENOISE_T_RESET empty it; hrt_scene_update_* does not.  Frame state, reservoirs, the present history, hrt_frame_times, a
+ *     pending progressive frame and hrt_denoise's own behaviour are untouched.
+ * Out of scope: object motion (a moved surface fails the plane test and restarts), sub-pixel jitter, filtering at display resolution,
+ * specular / diffuse separation. */
+enum hrt_denoise_temporal_flags { HRT_DENOISE_T_NO_DEMODULATE = 1u << 0, HRT_DENOISE_T_NO_SPATIAL = 1u << 1, HRT_DENOISE_T_RESET = 1u << 2 };
+typedef struct hrt_denoise_temporal_params {
+    int32_t  iterations;                          /* 1..8; 0 selects 5 (as hrt_denoise)                                  */
+    uint32_t flags;                               /* hrt_denoise_temporal_flags; any other bit: HRT_ERR_INVALID_ARG      */
+    float    alpha_color, alpha_moments;          /* <= 0 selects 0.2, 0.2 (SVGF): the floor of the blend factor         */
+    float    sigma_lum, sigma_normal, sigma_plane;   /* <= 0 selects 0.7, 0.5, 0.02; a NaN goes through.  sigma_lum is not SVGF's
+                                                     4: v is the variance of one frame's sample, not of the accumulated mean,
+                                                     and a band of 4 deviations of it blurs real detail     */
+    float    normal_cos_min, plane_tol;           /* history tap acceptance; <= 0 selects 0.9, 0.02                      */
+    int32_t  max_history;                         /* frames; <= 0 selects 64                                              */
+} hrt_denoise_temporal_params;
+int  hrt_denoise_temporal(hrt_ctx* ctx, const hrt_denoise_temporal_params* params, hrt_float3* out_radiance_host /* may be NULL */,
+                          int32_t* out_color_host /* may be NULL */, float* device_ms /* may be NULL */);
+/* slot 0 device pointers of the current history (all NULL, sizes 0 while it is empty): records of four floats per pixel.
+ * color[4 i .. 4 i + 2] = the accumulated (after iteration 0: filtered) demodulated colour, variance = color + 3;
+ * moments[4 i], [4 i + 1] = M1, M2, length = moments + 2; stride = 4 floats between pixels.  Valid until the next
+ * hrt_denoise_temporal (the planes swap) or anything that empties the history. */
+typedef struct hrt_denoise_history_views {
+    const float *color, *moments, *length, *variance;
+    int32_t width, height, stride, reserved;
+} hrt_denoise_history_views;
+int  hrt_denoise_history(hrt_ctx* ctx, hrt_denoise_history_views* out);
+/* The same two record planes copied to the host, for hosts without a device path of their own: color_host and moments_host (either
+ * may be NULL) receive width * height records of four floats, laid out as above.  Blocking, on slot 0's stream.  An empty history:
+ * HRT_ERR_INVALID_STATE. */
+int  hrt_denoise_history_read(hrt_ctx* ctx, float* color_host, float* moments_host);
 
 /* Test hooks (math probes, host-side builders of derived trees) are declared in hrt_test_hooks.h and exist only in
  * libhip_raytrace_test.so, the -DHRT_TEST_HOOKS build of the same sources; the shipped library exports none of them. */

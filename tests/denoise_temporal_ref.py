@@ -1,0 +1,203 @@
+"""tests/denoise_temporal_ref.py -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
+
+Restatement of the temporal denoiser (hrt_denoise_temporal), written from the contract in include/hip_raytrace.h ("temporal denoiser")
+alone: numpy float32, one elementary operation per numpy call, in the statement order of the contract, every pixel at once (a gathered
+or shifted view per tap keeps each pixel's own order).  Nothing of ilgpu_raytracing_amd/csrc is imported.  The shared functions of
+include/hrt_math.h (exp, fmax, fmin, tan) come from the oracle (orc.math_eval), as in tests/denoise_ref.py; sqrt, floor, abs and the
+divide are IEEE operations and numpy's own.
+"""
+import numpy as np
+
+from tests import denoise_ref as R
+from tests.taa_reproject_ref import cam_of
+
+f32 = np.float32
+G3 = np.array([1 / 4, 1 / 2, 1 / 4], np.float32)
+
+
+def make_fns(orc):
+    exp_fn, fmax_fn, pack_fn = R.make_fns(orc)
+    fmin_fn = lambda a, b: orc.math_eval("fmin", a, np.broadcast_to(f32(b), np.shape(a))).reshape(np.shape(a))
+    tan_fn = lambda x: orc.math_eval("tan", np.array([x], np.float32))[0]
+    return dict(exp=exp_fn, fmax=fmax_fn, fmin=fmin_fn, tan=tan_fn, pack=pack_fn)
+
+
+def defaults(iterations=0, alpha_color=0.0, alpha_moments=0.0, sigma_lum=0.0, sigma_normal=0.0, sigma_plane=0.0,
+             normal_cos_min=0.0, plane_tol=0.0, max_history=0):
+    """The parameter rules of hrt_denoise_temporal_params: a value <= 0 selects its default, an alpha > 1 is 1; a NaN goes through."""
+    pick = lambda v, d: f32(d) if f32(v) <= 0 else f32(v)
+    alpha = lambda v: f32(1.0) if pick(v, 0.2) > 1 else pick(v, 0.2)
+    return dict(iterations=5 if iterations == 0 else iterations, alpha_color=alpha(alpha_color), alpha_moments=alpha(alpha_moments),
+                sigma_lum=pick(sigma_lum, 0.7), sigma_normal=pick(sigma_normal, 0.5), sigma_plane=pick(sigma_plane, 0.02),
+                normal_cos_min=pick(normal_cos_min, 0.9), plane_tol=pick(plane_tol, 0.02),
+                max_history=f32(64 if max_history <= 0 else max_history))
+
+
+def lum(v):
+    return f32(0.2126) * v[..., 0] + f32(0.7152) * v[..., 1] + f32(0.0722) * v[..., 2]
+
+
+def _v(t):
+    return np.array(t, np.float32)
+
+
+class Temporal:
+    """One history, as one context keeps it.  step() is one hrt_denoise_temporal call; reset() is what hrt_reset_history, a scene
+    upload or HRT_DENOISE_T_RESET do.  After a step: color (h, w, 3), variance, length (h, w), moments (h, w, 2) hold the history;
+    step3_variance (h, w) is step 3's v of the last step with spatial passes."""
+
+    def __init__(self, fns):
+        self.fns = fns
+        self.reset()
+
+    def reset(self):
+        self.valid = False
+        self.size = None
+
+    def history(self):
+        return dict(color=self.color, variance=self.variance, moments=self.moments, length=self.length) if self.valid else None
+
+    def proj(self, cam, P, width, height):
+        p = P - _v(cam["origin"])
+        x, y, z = R._dot(p, _v(cam["right"])), R._dot(p, _v(cam["up"])), R._dot(p, _v(cam["forward"]))
+        ok = z > f32(1e-4)
+        t = self.fns["tan"](f32(0.5) * f32(cam["fovY"]))
+        ndc_x = x / (z * t * f32(cam["aspect"]))
+        ndc_y = y / (z * t)
+        return ok, f32(0.5) * (ndc_x + f32(1.0)) * f32(width), f32(0.5) * (ndc_y + f32(1.0)) * f32(height)
+
+    def step(self, frame, width, height, cam, demodulate=True, spatial=True, reset=False, pack=True, **kw):
+        """frame: as tests/denoise_ref.denoise takes it; cam: the frame's camera.  Returns (radiance (n, 3), colour (n,) or None)."""
+        fn = self.fns
+        exp_fn, fmax_fn, fmin_fn = fn["exp"], fn["fmax"], fn["fmin"]
+        q = defaults(**kw)
+        W, Hh = width, height
+        cam = cam_of(cam)
+        if self.size != (W, Hh) or reset:
+            self.valid = False
+        self.size = (W, Hh)
+        rad = np.asarray(frame["radiance"], np.float32).reshape(Hh, W, 3)
+        n = np.asarray(frame["gb_normalWS"], np.float32).reshape(Hh, W, 3)
+        P = np.asarray(frame["gb_worldPos"], np.float32).reshape(Hh, W, 3)
+        base = np.asarray(frame["gb_baseColor"], np.float32).reshape(Hh, W, 3)
+        depth = np.asarray(frame["depth"], np.float32).reshape(Hh, W)
+        hit = np.asarray(frame["gb_hitMask"]).reshape(Hh, W) != 0
+        zero, one = f32(0.0), f32(1.0)
+        with np.errstate(all="ignore"):
+            # 1. prepare
+            a = np.ones((Hh, W, 3), np.float32)
+            if demodulate:
+                a = np.where(hit[..., None], fmax_fn(base, 0.01), a).astype(np.float32)
+            c = rad / a
+            sp, sn = q["sigma_plane"], q["sigma_normal"]
+            kx = one / ((sp * sp) * fmax_fn(depth * depth, 1e-12))
+            kn = one / (sn * sn)
+            # 2. temporal
+            hn = np.zeros((Hh, W), np.float32)
+            hc = np.zeros((Hh, W, 3), np.float32)
+            hm1, hm2 = np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32)
+            if self.valid:
+                py, px = np.mgrid[0:Hh, 0:W]
+                okh, hx, hy = self.proj(self.cam, P, W, Hh)
+                okc, cx, cy = self.proj(cam, P, W, Hh)
+                qx, qy = px.astype(np.float32) + (hx - cx), py.astype(np.float32) + (hy - cy)
+                valid = okh & okc & (qx >= zero) & (qx <= f32(W - 1)) & (qy >= zero) & (qy <= f32(Hh - 1)) & hit
+                qx, qy = np.where(valid, qx, zero).astype(np.float32), np.where(valid, qy, zero).astype(np.float32)
+                x0f, y0f = np.floor(qx), np.floor(qy)
+                fx, fy = qx - x0f, qy - y0f
+                x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+                x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, Hh - 1)
+                tol = q["plane_tol"] * depth
+                ws = np.zeros((Hh, W), np.float32)
+                hs = np.zeros((Hh, W), np.float32)
+                pn, pP, phit = self.g_n, self.g_P, self.g_hit
+                for tx, ty, wt in ((x0, y0, (one - fx) * (one - fy)), (x1, y0, fx * (one - fy)),
+                                   (x0, y1, (one - fx) * fy), (x1, y1, fx * fy)):
+                    nt, Pt = pn[ty, tx], pP[ty, tx]
+                    take = valid & (wt > zero) & phit[ty, tx] & (R._dot(n, nt) >= q["normal_cos_min"]) & (np.abs(R._dot(Pt - P, n)) <= tol)
+                    ws = np.where(take, ws + wt, ws)
+                    hc = np.where(take[..., None], hc + wt[..., None] * self.color[ty, tx], hc)
+                    hm1 = np.where(take, hm1 + wt * self.moments[ty, tx, 0], hm1)
+                    hm2 = np.where(take, hm2 + wt * self.moments[ty, tx, 1], hm2)
+                    hs = np.where(take, hs + wt * self.length[ty, tx], hs)
+                some = ws > zero
+                hc = np.where(some[..., None], hc / ws[..., None], hc).astype(np.float32)
+                hm1, hm2 = np.where(some, hm1 / ws, hm1).astype(np.float32), np.where(some, hm2 / ws, hm2).astype(np.float32)
+                hn = np.where(some, hs / ws, zero).astype(np.float32)
+            l = lum(c)
+            fresh = ~(hn > zero)
+            N = fmin_fn(hn + one, q["max_history"])
+            r = one / N
+            ac, am = fmax_fn(r, q["alpha_color"]), fmax_fn(r, q["alpha_moments"])
+            Cb = hc + (c - hc) * ac[..., None]
+            M1b = hm1 + (l - hm1) * am
+            M2b = hm2 + (l * l - hm2) * am
+            C = np.where((fresh | ~hit)[..., None], c, Cb).astype(np.float32)
+            M1 = np.where(hit, np.where(fresh, l, M1b), zero).astype(np.float32)
+            M2 = np.where(hit, np.where(fresh, l * l, M2b), zero).astype(np.float32)
+            N = np.where(hit, np.where(fresh, one, N), zero).astype(np.float32)
+            self.moments = np.stack([M1, M2], -1)
+            self.length = N
+            self.g_n, self.g_P, self.g_hit, self.cam, self.valid = n.copy(), P.copy(), hit.copy(), cam, True
+            if not spatial:
+                # 5.
+                self.color, self.variance = C, np.zeros((Hh, W), np.float32)
+                out = (C * a).astype(np.float32).reshape(-1, 3)
+                return out, (fn["pack"](out) if pack else None)
+            # 3. variance
+            vm = fmax_fn(M2 - M1 * M1, 0.0)
+            S1, S2, sw = np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32)
+            if (hit & ~(N >= f32(4.0))).any():
+                for dy in range(-3, 4):
+                    for dx in range(-3, 4):
+                        hq = R._shift(hit, dx, dy, False)
+                        nq, Pq = R._shift(n, dx, dy), R._shift(P, dx, dy)
+                        dnv = n - nq
+                        dn = R._dot(dnv, dnv)
+                        d = R._dot(Pq - P, n)
+                        w = exp_fn(-(dn * kn + d * d * kx))
+                        take = hq & (w > zero)
+                        S1 = np.where(take, S1 + w * R._shift(M1, dx, dy), S1)
+                        S2 = np.where(take, S2 + w * R._shift(M2, dx, dy), S2)
+                        sw = np.where(take, sw + w, sw)
+            S1, S2 = S1 / sw, S2 / sw
+            vw = fmax_fn(S2 - S1 * S1, 0.0) * (f32(4.0) / N)
+            v = np.where(hit, np.where((N >= f32(4.0)) | ~(sw > zero), vm, vw), zero).astype(np.float32)
+            self.step3_variance = v                  # for tests of step 3 itself: not part of the history
+            # 4. a-trous
+            c = C
+            for i in range(q["iterations"]):
+                s = 1 << i
+                vs, gs = np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32)
+                for dy in range(-1, 2):
+                    for dx in range(-1, 2):
+                        hq = R._shift(hit, dx * s, dy * s, False)
+                        g = G3[dx + 1] * G3[dy + 1]
+                        vs = np.where(hq, vs + g * R._shift(v, dx * s, dy * s), vs)
+                        gs = np.where(hq, gs + g, gs)
+                vf = vs / gs
+                kl = one / (q["sigma_lum"] * np.sqrt(vf) + f32(1e-6))
+                lp = lum(c)
+                acc = np.zeros((Hh, W, 3), np.float32)
+                va, ws = np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32)
+                for dy in range(-2, 3):
+                    for dx in range(-2, 3):
+                        ox, oy = dx * s, dy * s
+                        hq = R._shift(hit, ox, oy, False)
+                        nq, Pq, cq, vq = R._shift(n, ox, oy), R._shift(P, ox, oy), R._shift(c, ox, oy), R._shift(v, ox, oy)
+                        dnv = n - nq
+                        dn = R._dot(dnv, dnv)
+                        d = R._dot(Pq - P, n)
+                        e = dn * kn + d * d * kx + np.abs(lp - lum(cq)) * kl
+                        w = (R.H5[dx + 2] * R.H5[dy + 2]) * exp_fn(-e)
+                        take = hq & (w > zero)
+                        acc = np.where(take[..., None], acc + w[..., None] * cq, acc)
+                        va = np.where(take, va + (w * w) * vq, va)
+                        ws = np.where(take, ws + w, ws)
+                done = hit & (ws > zero)
+                c = np.where(done[..., None], acc / ws[..., None], c).astype(np.float32)
+                v = np.where(done, va / (ws * ws), v).astype(np.float32)
+                if i == 0:
+                    self.color, self.variance = c, v
+            out = (c * a).astype(np.float32).reshape(-1, 3)
+        return out, (fn["pack"](out) if pack else None)
