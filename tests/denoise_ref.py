@@ -47,9 +47,44 @@ def _shift(a, dx, dy, fill=0):
     return out
 
 
-def denoise(frame, width, height, fns, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_plane=0.0, demodulate=True, pack=True):
+class SeamTaps:
+    """Test-only diagnostic, no part of the filter: which far taps counted.  The device kernels give every 32x8 tile of one
+    sub-lattice of step s (pixels with equal x mod s, y mod s) to a workgroup (tests/denoise_tiles.py); a tap of the outer ring
+    (|dx| == 2 or |dy| == 2) of a pixel near a tile border reads a record of the neighbour tile.  Per pass and axis this counts the
+    hit pixels that have such a tap inside the image (`could`) and those for which at least one of them was taken, w > 0 (`took`).
+    passes: one dict(step=s, x=(took, could), y=(took, could)) per a-trous pass, in order."""
+
+    def __init__(self):
+        self.passes = []
+
+    def begin(self, width, height, s, hit):
+        from tests.denoise_tiles import TILE_W, TILE_H
+        self.s, self.hit, self.size = s, hit, (width, height)
+        self.y, self.x = np.mgrid[0:height, 0:width]
+        self.tile = {"x": (self.x // s, TILE_W), "y": (self.y // s, TILE_H)}          # lattice coordinate u = x div s, tile = u div 32
+        self.took = {a: np.zeros((height, width), bool) for a in "xy"}
+        self.could = {a: np.zeros((height, width), bool) for a in "xy"}
+
+    def tap(self, dx, dy, take):
+        if max(abs(dx), abs(dy)) != 2:
+            return
+        w, h = self.size
+        qx, qy = self.x + dx * self.s, self.y + dy * self.s
+        inside = (qx >= 0) & (qx < w) & (qy >= 0) & (qy < h)
+        for a, d in (("x", dx), ("y", dy)):
+            u, t = self.tile[a]
+            other = self.hit & inside & ((u + d) // t != u // t)
+            self.could[a] |= other
+            self.took[a] |= other & take
+
+    def end(self):
+        self.passes.append(dict(step=self.s, **{a: (int(self.took[a].sum()), int(self.could[a].sum())) for a in "xy"}))
+
+
+def denoise(frame, width, height, fns, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_plane=0.0, demodulate=True, pack=True,
+            seam_taps=None):
     """frame: dict with radiance, gb_normalWS, gb_worldPos, gb_baseColor (n, 3) float32, depth (n,) float32, gb_hitMask (n,) int32.
-    Returns (denoised radiance (n, 3) float32, denoised colour (n,) int32 or None)."""
+    Returns (denoised radiance (n, 3) float32, denoised colour (n,) int32 or None).  seam_taps: an optional SeamTaps to fill."""
     exp_fn, fmax_fn, pack_fn = fns
     it, sc0, sn, sp = defaults(iterations, sigma_color, sigma_normal, sigma_plane)
     W, Hh = width, height
@@ -74,6 +109,8 @@ def denoise(frame, width, height, fns, iterations=0, sigma_color=0.0, sigma_norm
             kc = f32(1.0) / (sc * sc)
             acc = np.zeros((Hh, W, 3), np.float32)
             ws = np.zeros((Hh, W), np.float32)
+            if seam_taps is not None:
+                seam_taps.begin(W, Hh, s, hit)
             for dy in range(-2, 3):
                 for dx in range(-2, 3):
                     ox, oy = dx * s, dy * s
@@ -89,6 +126,10 @@ def denoise(frame, width, height, fns, iterations=0, sigma_color=0.0, sigma_norm
                     take = hq & (w > f32(0.0))
                     acc = np.where(take[..., None], acc + w[..., None] * cq, acc)
                     ws = np.where(take, ws + w, ws)
+                    if seam_taps is not None:
+                        seam_taps.tap(dx, dy, take)
+            if seam_taps is not None:
+                seam_taps.end()
             res = np.where((ws > f32(0.0))[..., None], acc / ws[..., None], c)
             c = np.where(hit[..., None], res, c).astype(np.float32)
         # 3. finish

@@ -66,8 +66,9 @@ class Temporal:
         ndc_y = y / (z * t)
         return ok, f32(0.5) * (ndc_x + f32(1.0)) * f32(width), f32(0.5) * (ndc_y + f32(1.0)) * f32(height)
 
-    def step(self, frame, width, height, cam, demodulate=True, spatial=True, reset=False, pack=True, **kw):
-        """frame: as tests/denoise_ref.denoise takes it; cam: the frame's camera.  Returns (radiance (n, 3), colour (n,) or None)."""
+    def step(self, frame, width, height, cam, demodulate=True, spatial=True, reset=False, pack=True, seam_taps=None, **kw):
+        """frame: as tests/denoise_ref.denoise takes it; cam: the frame's camera.  Returns (radiance (n, 3), colour (n,) or None).
+        seam_taps: an optional tests/denoise_ref.SeamTaps to fill from the a-trous passes (a diagnostic, no part of the filter)."""
         fn = self.fns
         exp_fn, fmax_fn, fmin_fn = fn["exp"], fn["fmax"], fn["fmin"]
         q = defaults(**kw)
@@ -180,6 +181,8 @@ class Temporal:
                 lp = lum(c)
                 acc = np.zeros((Hh, W, 3), np.float32)
                 va, ws = np.zeros((Hh, W), np.float32), np.zeros((Hh, W), np.float32)
+                if seam_taps is not None:
+                    seam_taps.begin(W, Hh, s, hit)
                 for dy in range(-2, 3):
                     for dx in range(-2, 3):
                         ox, oy = dx * s, dy * s
@@ -194,6 +197,10 @@ class Temporal:
                         acc = np.where(take[..., None], acc + w[..., None] * cq, acc)
                         va = np.where(take, va + (w * w) * vq, va)
                         ws = np.where(take, ws + w, ws)
+                        if seam_taps is not None:
+                            seam_taps.tap(dx, dy, take)
+                if seam_taps is not None:
+                    seam_taps.end()
                 done = hit & (ws > zero)
                 c = np.where(done[..., None], acc / ws[..., None], c).astype(np.float32)
                 v = np.where(done, va / (ws * ws), v).astype(np.float32)
