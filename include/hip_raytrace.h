@@ -65,6 +65,9 @@
  * one-process-per-GPU host are refused while reuse is on.
  *
  * Status codes: 0 = ok, negative = error (message via hrt_last_error).
+ *
+ * Caller memory: an entry point writes exactly the bytes its contract names in caller memory (host or device), at the stated
+ * minimum alignment and no more, and never modifies an input array (tests/test_guard_bands_gpu.py holds every entry point to it).
  */
 #ifndef HIP_RAYTRACE_H
 #define HIP_RAYTRACE_H
