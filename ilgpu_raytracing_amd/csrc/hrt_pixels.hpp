@@ -11,7 +11,7 @@ using namespace hrt;
 // camera through a compact square and walk nearly the same BVH nodes.  Workgroup ids are
 // dealt round-robin over the 8 XCDs by the dispatcher; remap() hands every XCD one
 // contiguous band of tiles so each private 4 MiB L2 caches one region of the BVH instead
-// of all of it (bijective form of the T1 remap, cdna_hip_programming.md).  Frames of a small scene (<= kSmallSceneNodes in
+// of all of it (bijective form of the T1 remap, cdna_hip_programming.md).  Frames of a small scene (<= kSmallSceneNodes, hrt_scene.hip, in
 // the fused kernels) skip the remap (band = 0): their BVH is a few cache lines, and the identity map gives every XCD tiles from
 // the whole image (60 tiles per row is not a multiple of 8), so no XCD waits on the heaviest band of rows.
 // ---------------------------------------------------------------------------------------

@@ -1,5 +1,8 @@
-// hrt_runtime.hip -- libhip_raytrace.so: kernels' entry points + the C ABI of
-// include/hip_raytrace.h (context, scene upload, frame render, multi-device row tiling).
+// hrt_runtime.hip -- libhip_raytrace.so: kernels' entry points + the part of the C ABI of
+// include/hip_raytrace.h that launches them (context, frame render, multi-device row tiling,
+// presentation, motion vectors, queries, denoisers) + the test hooks.  The scene entry points
+// are hrt_scene.hip's; what the host units share is hrt_ctx.hpp.  Host code that launches no
+// kernel of this unit does not belong here.
 //
 // Replaces the ILGPU accelerator / kernel-launch layer of the reference
 // (Engine/RTRenderer.cs:66-68,85-86,118-120,152-153,164,181-205,233; Engine/Scene.cs:258-279,
@@ -19,6 +22,7 @@
 #include <cmath>
 #include <cfloat>
 #include <utility>
+#include "hrt_ctx.hpp"
 #include "hrt_device.hpp"
 #include "hrt_trace_packed.hpp"
 #include "hrt_wavefront.hpp"
@@ -32,10 +36,12 @@
 #include "hrt_denoise_temporal.hpp"
 #include "../../include/hip_raytrace.h"
 #ifdef HRT_TEST_HOOKS
+#include "hrt_scene_pack.hpp"          // the host-only hooks call the scene validator and the second tree's host code
 #include "../../include/hrt_test_hooks.h"
 #endif
 
 using namespace hrt;
+using namespace hrt::detail;
 
 
 #include "hrt_pixels.hpp"
@@ -517,155 +523,11 @@ __global__ void hrt_math_exhaustive_kernel(int which, unsigned long long* mismat
 // ---------------------------------------------------------------------------------------
 namespace {
 
-thread_local std::string g_create_error;
-TreeletLimits g_treelet_limits;              // shipped values unless a test lowered them (hrt_debug_set_treelet_limits)
-
-#ifndef HRT_BATCH_LANES
-#define HRT_BATCH_LANES 2
-#endif
-constexpr int kMaxLanes = 4, kBatchLanes = HRT_BATCH_LANES;      // sample batches in flight: 1 / 2 / 3 / 4 measured on configs 4 / 5 at 64 / 256 spp: 362 / 328 / 334 / 325 ms and 1412 / 1323 / 1376 / 1330 ms
-static_assert(kBatchLanes >= 1 && kBatchLanes <= kMaxLanes, "");
-
-// Grow-only device (or pinned host) memory of one DeviceState.  It never shrinks and is reallocated only when it is too small.
-struct Scratch {
-    void* p = nullptr; size_t bytes = 0;
-    enum Drain { kStream, kDevice };           // what grow() waits for before it frees the old block (work enqueued earlier may use it)
-    int grow(hrt_ctx* c, size_t need, hipStream_t st, Drain drain = kStream, bool pinned = false);     // no-op when need <= bytes
-    void release(bool pinned = false);
-};
-
-struct DeviceState {
-    int device_id = -1;
-    int n_cu = 256;                            // compute units (MI355X: 256)
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;             // shadow walks run beside the closest-hit walks of the same bounce
-    static constexpr int kRing = 128;          // frames that may be in flight between two syncs
-    hipEvent_t ev[kRing][4] = {};
-    int ring_head = 0;                         // frames enqueued since the last synchronize
-    bool ring_counts = false;
-    std::vector<float> frame_ms[2];            // per-frame HIP-event times (launch 1, path-trace stage) of the frames the last hrt_synchronize collected
-    // scene (15 arrays)
-    void* scene[15] = {};
-    DScene dscene{};
-    void* packed[7] = {};                      // NodeQ tlas, FInst, NodeQ blas, FTri, NodeQ TLAS leaves in walk order (device-private repack)
-    DPacked dpacked{};
-    TlasDevice tl{};                           // device-side TLAS maintenance (hrt_bvh.hpp); aux arrays below
-    void* tlaux[10] = {};                      // parent, nchild, arrive, scanIn, scanOut, sa, flags, cost, saBase, scanTmp + costPartial
-    void* tlscratch = nullptr;                 // LBVH scratch, allocated on the first rebuild
-    // a second tree over the same instances, built on the device at upload: what boolean queries of fast-sphere scenes walk
-    TlasDevice tl2{};
-    void* tl2mem[18] = {};          // [14] slot map, [15] renumbered copies, [16] what they permute, [17] scratch of the slot map
-    bool any_built = false;                    // a second tree exists for this scene (any_ok: and it describes the scene as it is now)
-    size_t ordX = 0, ordP = 0;                 // records in the renumbered copies of tlasX / of tlas
-    DPacked dpackedAny{};
-    bool any_ok = false;
-    bool tlas_base_valid = false;              // saBase holds the node areas of the TLAS as it was last built
-    bool tlas_lbvh = false;                    // the TLAS in use was BUILT on the device (Auto rebuilds an uploaded tree once: the LBVH walks faster)
-    BlasDevice bl{};                           // triangle-mesh BLAS maintenance after vertex updates
-    void* blaux[12] = {};                      // parent, nchild, subend, orig, arrive, ids of the TriMesh instances, kind, ids of the SphereSet instances, sa, saBase, growPartial, grow
-    int n_mesh_inst = 0, n_sphere_inst = 0;
-    // treelets of the big triangle-mesh BLASes (hrt_treelets.hpp) and the queues of the treelet walker, per batch lane and walk kind (0 shadow, 1 closest)
-    void* tlmem[3] = {};                       // reduced trees, treelet table, BLAS root -> reduced root
-    DTreelets dtl{};
-    bool tl_ok = false;                        // the treelets describe the BLASes as they are now (a vertex update or BLAS rebuild drops them)
-    Scratch tlq_mem[kMaxLanes];
-    int max_lds = 65536;                       // LDS a workgroup may ask for
-    bool blas_base_valid = false;              // saBase holds the node areas of the mesh BLASes as they were last built
-    // presentation (TAAU history + display-size colour), device slot 0 only
-    int32_t *present_color = nullptr, *taa_hist_color = nullptr, *taa_hist_obj = nullptr;
-    int present_w = 0, present_h = 0; bool taa_history_valid = false;
-    // HRT_PRESENT_TAAU_REPROJECT: the pair a reprojecting resolve writes while it reads the current one (swapped after the launch;
-    // allocated by the first such present), and the camera of the frame last resolved into the history (valid with the history)
-    int32_t *taa_spare_color = nullptr, *taa_spare_obj = nullptr;
-    hrt_camera taa_hist_cam{};
-    float present_ms = 0.f;                    // HIP-event time of the last hrt_present's kernel (hrt_present_time)
-    // streamed path-trace workspace
-    // two sample batches are in flight at a time (lane 0 on stream / stream2, lane 1 on stream3 / stream4): each has its own workspace
-    Scratch wf_mem[kMaxLanes], wf_cnt[kMaxLanes];   // path state (float planes) and counters (ints) of a lane
-    Scratch wf_accum;                          // Lframe carried across the batches of a frame (one plane set of floats, shared)
-    hipStream_t laneStream[kMaxLanes][2] = {};  // lanes >= 1: main and side stream (lane 0 uses stream / stream2)
-    hipEvent_t evLane[kMaxLanes][3] = {};      // per lane: fork, join, resolve done
-    hipEvent_t evStage = nullptr;
-    Scratch split_mem;                         // fused kernel in sample groups: per-sample radiance + staged reservoirs (floats)
-    // per-pixel buffers, full image size on every device (rows outside the tile stay untouched)
-    int64_t nPix = 0;
-    DGBuffer gb{};
-    DFramebuffer fb{};
-    DReservoir resA{}, resB{};
-    hrt_float3* prog_carry = nullptr;          // hrt_render_progressive: raw sample sum (Lframe before 1/spp) per global pixel index, 12 B/px;
-                                               // allocated by the first progressive call, at the size of the per-pixel buffers
-    unsigned long long* counters = nullptr;   // 2 x 10
-    int row_begin = 0, row_end = 0;            // rows [row_begin,row_end) ...
-    int strip_n = 1, strip_i = 0;              // ... of which this device owns 8-row strips s with s % strip_n == strip_i
-    int n_strips = 0;
-    // caller-ray queries (hrt_trace_rays / hrt_trace_hits / hrt_trace_paths): one chunk in flight, shared by the three and carved per
-    // chunk by ChunkStager; grown on demand and separate from the frame's buffers, so hrt_device_views pointers never move because of a
-    // query and a radiance chunk's G-buffer and sample-group scratch never live in the frame's
-    Scratch q_dev;                             // the chunk's device workspace, then (host path) its staged caller arrays
-    Scratch q_pin;                             // pinned staging of the host path: the chunk's caller arrays
-    hipEvent_t q_ev[2] = {};                   // bracket the kernels of a chunk; hrt_present and hrt_motion_vectors time theirs with them too
-    // hrt_motion_vectors, host path: the slot's vectors before they are gathered (8 B per pixel, global pixel index)
-    Scratch mv_mem;
-    // hrt_denoise, device slot 0 only: guide records (32 B per pixel), two colour planes (16 B each), then the two result planes
-    // (denoised radiance 12 B, packed colour 4 B); dn_pix = the frame size they were allocated for
-    Scratch dn_mem;
-    int64_t dn_pix = 0;
-    hrt_float3* dn_radiance = nullptr;
-    int32_t* dn_color = nullptr;
-    // hrt_denoise_temporal, device slot 0 only: two guide sets (32 B per pixel each), two history colour and two history moment planes
-    // (16 B each); set dt_cur holds what the last call wrote.  dt_valid: the history is not empty; dt_cam: the camera of the frame it
-    // was last accumulated from (what the next call reprojects from)
-    Scratch dt_mem;
-    int dt_w = 0, dt_h = 0, dt_cur = 0;
-    bool dt_valid = false;
-    hrt_camera dt_cam{};
-};
+thread_local std::string g_create_error;       // the error text of calls without a context, per calling thread
 
 } // namespace
 
-struct hrt_ctx {
-    std::vector<DeviceState> dev;
-    std::string err;
-    bool scene_ready = false;
-    bool packed_ok = false;                    // false: scene exceeds the packed layout's limits -> TracerRef
-    int packed_feat = 3;                       // TracerPackedT<FEAT> variant of the committed scene
-    int flat_leaves = 0;                       // > 0: TLAS leaves of a fast-sphere-only scene that fits TracerFlat
-    bool own_in_world = false;                 // PackedHost::own_in_world of the uploaded scene
-    bool small_scene = false;                  // <= kSmallSceneNodes BVH nodes: the walk is ALU-bound and L1-resident -> megakernel
-    // state of hrt_scene_update_instances
-    bool refit_ok = false;                     // every reachable TLAS node has one parent and <= 64 children
-    bool feat_alpha = false;                   // the triangle half of packed_feat (does not change with the TLAS)
-    int64_t n_inst = 0, n_tlas = 0, n_slots = 0, n_blas = 0;
-    int tlas_leaves = 0;                       // reachable leaves of the TLAS in use
-    bool tlas_on_device = false;               // the TLAS in use was refitted / rebuilt on the device (walk-order numbering)
-    bool blas_refit_ok = false;                // hrt_scene_update_positions can refit every triangle-mesh BLAS
-    bool blas_rebuild_ok = false;              // ... and rebuild it (HRT_REBUILD_BLAS)
-    std::vector<MeshJob> mesh_jobs;
-    int max_mesh_items = 0;
-    int64_t n_positions = 0, n_spheres = 0;
-    int64_t scene_count[15] = {};
-    int width = 0, height = 0;
-    hrt_camera frame_cam{}, frame_prev_cam{};  // cam / prevCam of the last frame call (what gb_worldPos was rendered from)
-    uint64_t frame_serial = 0;                 // counts frame calls and scene uploads: what the denoised planes are checked against
-    uint64_t dn_serial = 0;                    // frame_serial of the frame hrt_denoise or hrt_denoise_temporal last ran on (0: never)
-    uint64_t dt_serial = 0;                    // frame_serial of the frame hrt_denoise_temporal last accumulated (0: never)
-    long long max_resident_paths = 0;          // hrt_set_workspace_limit: 0 = kWfMaxPaths
-    std::vector<std::pair<char*, size_t>> pinned;   // hrt_host_register: page-locked ranges of the caller (gather targets)
-    // the progressive frame a continuation (hrt_render_progressive with sample_begin > 0) may extend: what its last call rendered.
-    // Cleared by every call that changes what the next samples would see (frames, scene changes, history reset).
-    struct {
-        bool valid = false;
-        hrt_frame_params p{};                  // params of the last call; p.spp = samples rendered so far
-        int rb = 0, re = 0, sn = 1, si = 0;    // row range and strips, normalised as the render call normalises them
-        uint32_t pathFlags = 0;                // HRT_FLAG_REFERENCE_LAYOUT | MEGAKERNEL | STREAMED | TREELETS of the calls
-    } prog;
-};
-
-namespace {
-
-const size_t kSceneElem[15] = {sizeof(hrt_bvh_node), 4, sizeof(hrt_instance), sizeof(hrt_bvh_node), 4, sizeof(hrt_sphere), 4,
-                               sizeof(hrt_float3), sizeof(hrt_mesh_tri), sizeof(hrt_float2), sizeof(hrt_mesh_tri_uv), 4,
-                               sizeof(hrt_material), sizeof(hrt_rgba32), sizeof(hrt_tex_info)};
+namespace hrt { namespace detail {
 
 int fail(hrt_ctx* c, int code, const std::string& msg)
 {
@@ -686,14 +548,6 @@ int on_exception(hrt_ctx* c, const char* who) noexcept
     catch (...) { return HRT_ERR_OUT_OF_MEMORY; }      // not even the message could be stored
 }
 
-#define HIPCHK(ctx, expr)                                                                          \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return fail(ctx, e__ == hipErrorOutOfMemory ? HRT_ERR_OUT_OF_MEMORY : HRT_ERR_HIP,     \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                       \
-    } while (0)
-
 int Scratch::grow(hrt_ctx* c, size_t need, hipStream_t st, Drain drain, bool pinned)
 {
     if (need <= bytes) return HRT_OK;
@@ -709,9 +563,6 @@ void Scratch::release(bool pinned)
     p = nullptr; bytes = 0;
 }
 
-// Runs fn(slot, ec) once per device slot: inline with ec = c, or, with `threads`, on one host thread per slot with ec = nullptr, so
-// that fn's error text lands in the worker's own g_create_error.  A call that blocks its issuing thread (a copy into pageable memory,
-// a synchronise) would otherwise serialise the slots.  Reports the first failing slot as "<who>: <what>device slot <i>: <text>".
 int for_each_slot(hrt_ctx* c, bool threads, const char* who, const char* what, const std::function<int(int, hrt_ctx*)>& fn)
 {
     const int nd = (int)c->dev.size();
@@ -733,6 +584,10 @@ int for_each_slot(hrt_ctx* c, bool threads, const char* who, const char* what, c
         if (rcs[(size_t)i] != HRT_OK) return fail(c, rcs[(size_t)i], std::string(who) + ": " + what + "device slot " + std::to_string(i) + ": " + errs[(size_t)i]);
     return HRT_OK;
 }
+
+}} // namespace hrt::detail
+
+namespace {
 
 void free_pixels(DeviceState& d)
 {
@@ -813,457 +668,6 @@ void free_workspace(DeviceState& d)
     d.split_mem.release();
 }
 
-void free_scene(DeviceState& d)
-{
-    for (int i = 0; i < 15; i++) { if (d.scene[i]) (void)hipFree(d.scene[i]); d.scene[i] = nullptr; }
-    for (int i = 0; i < 7; i++) { if (d.packed[i]) (void)hipFree(d.packed[i]); d.packed[i] = nullptr; }
-    for (int i = 0; i < 10; i++) { if (d.tlaux[i]) (void)hipFree(d.tlaux[i]); d.tlaux[i] = nullptr; }
-    for (int i = 0; i < 18; i++) { if (d.tl2mem[i]) (void)hipFree(d.tl2mem[i]); d.tl2mem[i] = nullptr; }
-    d.tl2 = TlasDevice{}; d.any_ok = false; d.any_built = false; d.ordX = d.ordP = 0;
-    if (d.tlscratch) (void)hipFree(d.tlscratch);
-    d.tlscratch = nullptr; d.tl = TlasDevice{}; d.tlas_base_valid = false; d.tlas_lbvh = false;
-    for (int i = 0; i < 12; i++) { if (d.blaux[i]) (void)hipFree(d.blaux[i]); d.blaux[i] = nullptr; }
-    d.bl = BlasDevice{}; d.n_mesh_inst = 0; d.n_sphere_inst = 0; d.blas_base_valid = false;
-    for (int i = 0; i < 3; i++) { if (d.tlmem[i]) (void)hipFree(d.tlmem[i]); d.tlmem[i] = nullptr; }
-    d.dtl = DTreelets{}; d.tl_ok = false;
-}
-
-// ---------------------------------------------------------------------------------------
-// Scene validation + repack (host, once per commit).
-// Validation: every index a kernel will dereference is range-checked and the node graphs are
-// checked to be acyclic, so a malformed scene is an HRT_ERR_INVALID_ARG here instead of a GPU
-// fault or a walk that never ends.  (The reference trusts its own builder and checks nothing.)
-// ---------------------------------------------------------------------------------------
-struct PackedHost {
-    std::vector<NodeQ> tlas, blas, flat;     // flat: the TLAS leaves in walk order (TracerFlat)
-    std::vector<FInst> finst;
-    std::vector<FTri> ftri;
-    std::vector<NodeQ> tlasX; // FEAT 0: TLAS with instance records inlined after their leaf (walker)
-    int n_tlasX = 0;          // records in tlasX (0: not built)
-    int n_flat = 0;           // leaves in `flat` (0: scene does not qualify)
-    std::vector<int32_t> parent, nchild;     // TLAS, packed numbering: parent of a node (-1: none), children of an inner node
-    std::vector<int32_t> bparent, bnchild, bsubend, borig;   // BLAS nodes of triangle meshes, packed numbering: parent (-1 root, -2 not maintained),
-                                                             // children, end of the subtree's index range, index in the uploaded numbering
-    std::vector<int32_t> bkind;                              // 0: node of no maintained BLAS, 1: triangle mesh, 2: sphere set
-    int max_range[3] = {0, 0, 0};                            // largest node range of a maintained BLAS, per kind
-    std::vector<int32_t> sphereInst;                         // ids of the SphereSet instances whose BLAS is maintained
-    std::vector<int32_t> meshInst;                           // ids of the TriMesh instances whose BLAS is maintained
-    std::vector<MeshJob> meshJobs;                           // the same, with what a device-side rebuild of the BLAS needs
-    std::vector<std::pair<int64_t, int64_t>> meshRanges;     // node ranges of the maintained triangle-mesh BLASes (walk order): candidates for treelets
-    bool blas_rebuild_ok = true;                             // every mesh's leaves list their triangles in one region of triPrimIdx
-    bool blas_refit_ok = true;                               // every TriMesh BLAS can be refitted on the device
-    bool refit_ok = true;     // the TLAS can be refitted bottom-up on the device (hrt_bvh.hpp)
-    int reach_leaves = 0;     // reachable TLAS leaves
-    bool nested = true;       // every reachable TLAS node's box lies inside its parent's, every fast-sphere instance's own box inside its leaf's:
-                              // what "the boxes above only accelerate" (TracerFlat, the second tree) needs; the builders guarantee it, an uploaded tree may not
-    bool own_in_world = true; // every fast-sphere instance's own box (its one-node BLAS) lies inside its worldBounds: a TLAS refitted or rebuilt on the
-                              // device (leaf boxes = unions of worldBounds) is then nested like the builder's; false e.g. for an instance whose BLAS
-                              // the position-indexed builder put over another sphere (Scene.cs:386-395)
-    bool inst_once = false;   // the reachable TLAS leaves list every instance exactly once (a second tree over "the instances" answers the same queries)
-    bool ok = true;           // false -> limits of the packed encoding exceeded (not an error)
-    int feat = 0;             // TracerPackedT<FEAT> bits the committed scene needs
-};
-
-inline float bits_f(int v) { float f; std::memcpy(&f, &v, 4); return f; }
-inline float4 mkf4(float x, float y, float z, float w) { float4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-
-bool is_identity(const hrt_affine3x4& m)
-{
-    return m.m00 == 1.f && m.m01 == 0.f && m.m02 == 0.f && m.m03 == 0.f && m.m10 == 0.f && m.m11 == 1.f && m.m12 == 0.f && m.m13 == 0.f &&
-           m.m20 == 0.f && m.m21 == 0.f && m.m22 == 1.f && m.m23 == 0.f;
-}
-
-// nodes[lo,hi): every link in {-1} U [lo,hi) (TLAS: lo = 0), walk graph (left edge of inner nodes, skip edge of
-// all nodes) acyclic from `root`.  Returns "" or an error text.
-std::string check_nodes(const hrt_bvh_node* nodes, int64_t lo, int64_t hi, int64_t root, int64_t leafLimit, const char* what)
-{
-    if (hi <= lo) return "";
-    for (int64_t i = lo; i < hi; i++)
-    {
-        const hrt_bvh_node& n = nodes[i];
-        if (n.skipIndex < -1 || n.skipIndex >= hi) return std::string(what) + ": skipIndex out of range";   // skip may leave a BLAS range upward? no: reference skips are -1 or inside
-        if (n.skipIndex != -1 && n.skipIndex < lo) return std::string(what) + ": skipIndex below its BLAS";
-        if (n.count > 0) { if (n.first < 0 || (int64_t)n.first + n.count > leafLimit) return std::string(what) + ": leaf range outside the index list"; }
-        else if (n.left < -1 || n.left >= hi || (n.left != -1 && n.left < lo)) return std::string(what) + ": left child out of range";
-    }
-    // iterative DFS, colours: 0 new, 1 on stack, 2 done
-    std::vector<uint8_t> col((size_t)(hi - lo), 0);
-    std::vector<std::pair<int64_t, int>> st;
-    st.emplace_back(root, 0);
-    col[(size_t)(root - lo)] = 1;
-    while (!st.empty())
-    {
-        auto& top = st.back();
-        const hrt_bvh_node& n = nodes[top.first];
-        int64_t next = -2;
-        if (top.second == 0) { top.second = 1; next = n.count > 0 ? -1 : n.left; }
-        else if (top.second == 1) { top.second = 2; next = n.skipIndex; }
-        else { col[(size_t)(top.first - lo)] = 2; st.pop_back(); continue; }
-        if (next < 0) continue;
-        uint8_t& c = col[(size_t)(next - lo)];
-        if (c == 1) return std::string(what) + ": node links form a cycle";
-        if (c == 0) { c = 1; st.emplace_back(next, 0); }
-    }
-    return "";
-}
-
-std::string validate_and_pack(const hrt_scene_desc* s, PackedHost& out)
-{
-    const int64_t nT = s->n_tlasNodes, nTI = s->n_tlasInstanceIndices, nI = s->n_instances, nB = s->n_blasNodes;
-    const int64_t nSP = s->n_spherePrimIdx, nS = s->n_spheres, nTP = s->n_triPrimIdx, nPos = s->n_meshPositions, nTri = s->n_meshTris;
-    const int64_t nTC = s->n_meshTexcoords, nTU = s->n_meshTriUVs, nTM = s->n_triMatIndex, nM = s->n_materials, nTx = s->n_texels, nTxI = s->n_texInfos;
-    for (int64_t v : {nT, nTI, nI, nB, nSP, nS, nTP, nPos, nTri, nTC, nTU, nTM, nM, nTx, nTxI})
-        if (v > 0x7FFFFFF0LL) return "array too long for 32-bit indices";
-    for (int64_t i = 0; i < nTI; i++) if (s->tlasInstanceIndices[i] < 0 || s->tlasInstanceIndices[i] >= nI) return "tlasInstanceIndices entry out of range";
-    for (int64_t i = 0; i < nSP; i++) if (s->spherePrimIdx[i] < 0 || s->spherePrimIdx[i] >= nS) return "spherePrimIdx entry out of range";
-    for (int64_t i = 0; i < nTP; i++) if (s->triPrimIdx[i] < 0 || s->triPrimIdx[i] >= nTri) return "triPrimIdx entry out of range";
-    if (nTri > 0 && (nTM < nTri || nTU < nTri)) return "triMatIndex / meshTriUVs shorter than meshTris";
-    const int64_t limTC = nTC > 0 ? nTC : 1, limM = nM > 0 ? nM : 1;      // an empty list is one zeroed element (Scene.cs:370-377)
-    for (int64_t i = 0; i < nTri; i++)
-    {
-        const hrt_mesh_tri& t = s->meshTris[i];
-        if (t.i0 < 0 || t.i1 < 0 || t.i2 < 0 || t.i0 >= nPos || t.i1 >= nPos || t.i2 >= nPos) return "meshTris vertex index out of range";
-        const hrt_mesh_tri_uv& u = s->meshTriUVs[i];
-        if (u.t0 < 0 || u.t1 < 0 || u.t2 < 0 || u.t0 >= limTC || u.t1 >= limTC || u.t2 >= limTC) return "meshTriUVs index out of range";
-        if (s->triMatIndex[i] < 0 || s->triMatIndex[i] >= limM) return "triMatIndex entry out of range";
-    }
-    for (int64_t i = 0; i < nTxI; i++)
-    {
-        const hrt_tex_info& ti = s->texInfos[i];
-        if (ti.Width > 0 && ti.Height > 0 && (ti.Offset < 0 || (int64_t)ti.Offset + (int64_t)ti.Width * ti.Height > nTx)) return "texInfos entry outside texels";
-    }
-    if (nT > 0) { std::string e = check_nodes(s->tlasNodes, 0, nT, 0, nTI, "tlasNodes"); if (!e.empty()) return e; }
-    for (int64_t i = 0; i < nI; i++)
-    {
-        const hrt_instance& in = s->instances[i];
-        if (in.blasNodeCount < 0 || in.blasRoot < 0 || (int64_t)in.blasRoot + in.blasNodeCount > nB) return "instance BLAS range outside blasNodes";
-        if (in.blasNodeCount == 0) continue;
-        std::string e = check_nodes(s->blasNodes, in.blasRoot, (int64_t)in.blasRoot + in.blasNodeCount, in.blasRoot,
-                                    in.type == HRT_BLAS_SPHERESET ? nSP : nTP, "blasNodes");
-        if (!e.empty()) return e;
-    }
-
-    // ---- repack
-    // Nodes are renumbered into walk order (depth-first, hit edge before skip edge): the child a ray enters after
-    // a hit is the next node in memory, so a descent reads consecutive 32-byte records (4 per 128-byte line)
-    // instead of jumping between the two halves of the builder's right-first numbering.  Pure permutation: every
-    // walk visits the same nodes in the same order.  perm[old - lo] = new - lo.
-    auto walk_order = [&](const hrt_bvh_node* src, int64_t lo, int64_t hi, int64_t root, std::vector<int32_t>& perm) -> int32_t {   // returns the number of reachable nodes
-        const size_t n = (size_t)(hi - lo);
-        perm.assign(n, -1);
-        int32_t next = 0;
-        std::vector<int64_t> st;
-        st.push_back(root);
-        while (!st.empty())
-        {
-            const int64_t i = st.back(); st.pop_back();
-            if (i < lo || i >= hi || perm[(size_t)(i - lo)] >= 0) continue;
-            perm[(size_t)(i - lo)] = next++;
-            const hrt_bvh_node& b = src[i];
-            st.push_back(b.skipIndex);
-            if (b.count <= 0) st.push_back(b.left);
-        }
-        const int32_t reachable = next;
-        for (size_t i = 0; i < n; i++) if (perm[i] < 0) perm[i] = next++;        // unreachable nodes keep a slot
-        return reachable;
-    };
-    auto pack_range = [&](const hrt_bvh_node* src, int64_t lo, int64_t hi, const std::vector<int32_t>& perm, std::vector<NodeQ>& dst) {
-        auto remap = [&](int32_t link) -> int { return (link < lo || link >= hi) ? kEnd : (int)(lo + perm[(size_t)(link - lo)]); };
-        for (int64_t i = lo; i < hi; i++)
-        {
-            const hrt_bvh_node& b = src[i];
-            int cnt = b.count > 0 ? b.count : 0;
-            if (cnt > 15) out.ok = false;
-            int link = cnt > 0 ? b.first : remap(b.left);
-            int hiw = remap(b.skipIndex) | (int)((unsigned)(cnt & 15) << 28);
-            NodeQ& q = dst[(size_t)(lo + perm[(size_t)(i - lo)])];
-            q.lo = mkf4(b.boundsMin.X, b.boundsMin.Y, b.boundsMin.Z, bits_f(link));
-            q.hi = mkf4(b.boundsMax.X, b.boundsMax.Y, b.boundsMax.Z, bits_f(hiw));
-        }
-    };
-    auto alloc_nodes = [&](int64_t n, std::vector<NodeQ>& dst) {
-        dst.resize((size_t)std::max<int64_t>(n, 1));
-        std::memset(dst.data(), 0, dst.size() * sizeof(NodeQ));
-        if (n == 0) { dst[0].lo.w = bits_f(kEnd); dst[0].hi.w = bits_f(kEnd); }    // the 1-element zero buffer: count 0, left 0 -> treat as end
-        if (n >= kEnd) out.ok = false;
-    };
-    std::vector<int32_t> perm;
-    alloc_nodes(nT, out.tlas);
-    int32_t reachableT = -1;
-    if (nT > 0) { reachableT = walk_order(s->tlasNodes, 0, nT, 0, perm); pack_range(s->tlasNodes, 0, nT, perm, out.tlas); }
-    {   // parents and child counts for the device refit: the children of an inner node are the chain left, left.skip, ...
-        // up to the node's own skip link (two nodes for both builders)
-        const size_t n = out.tlas.size();
-        out.parent.assign(n, -1); out.nchild.assign(n, 0);
-        auto cntq = [&](size_t i) { return (int)((unsigned)__builtin_bit_cast(int, out.tlas[i].hi.w) >> 28); };
-        auto skipq = [&](size_t i) { return __builtin_bit_cast(int, out.tlas[i].hi.w) & kEnd; };
-        for (size_t i = 0; i < (size_t)nT; i++)
-        {
-            if (cntq(i) > 0) { if ((int32_t)i < reachableT) out.reach_leaves++; continue; }
-            int c = __builtin_bit_cast(int, out.tlas[i].lo.w) & kEnd;
-            const int end = skipq(i);
-            int steps = 0;
-            while (c != kEnd && c != end)
-            {
-                if (c == 0 || out.parent[(size_t)c] != -1 || ++steps > 64) { out.refit_ok = false; break; }
-                out.parent[(size_t)c] = (int32_t)i; out.nchild[i]++;
-                c = skipq((size_t)c);
-            }
-        }
-        if (nT == 0) out.refit_ok = false;
-        // does the walk meet every instance exactly once?
-        std::vector<uint8_t> seen((size_t)std::max<int64_t>(nI, 1), 0);
-        bool once = nT > 0 && out.refit_ok;
-        for (size_t i = 0; once && i < (size_t)nT; i++)
-        {
-            if (cntq(i) == 0 || (int32_t)i >= reachableT) continue;
-            const int first = __builtin_bit_cast(int, out.tlas[i].lo.w);
-            for (int j = 0; j < cntq(i); j++)
-            {
-                const int64_t slot = (int64_t)first + j;
-                if (slot < 0 || slot >= nTI) { once = false; break; }
-                const int64_t ii = s->tlasInstanceIndices[slot];
-                if (ii < 0 || ii >= nI || seen[(size_t)ii]++) { once = false; break; }
-            }
-        }
-        for (int64_t ii = 0; once && ii < nI; ii++) if (!seen[(size_t)ii]) once = false;
-        out.inst_once = once;
-        auto inside = [](const NodeQ& c, const NodeQ& p) {
-            // false with a NaN.  The child has to be a regular box (min <= max) too: the slab test reads an inverted box as its
-            // mirror image, which these comparisons say nothing about
-            return c.lo.x <= c.hi.x && c.lo.y <= c.hi.y && c.lo.z <= c.hi.z &&
-                   c.lo.x >= p.lo.x && c.lo.y >= p.lo.y && c.lo.z >= p.lo.z && c.hi.x <= p.hi.x && c.hi.y <= p.hi.y && c.hi.z <= p.hi.z;
-        };
-        for (size_t i = 1; i < (size_t)nT; i++)
-            if ((int32_t)i < reachableT && out.parent[i] >= 0 && !inside(out.tlas[i], out.tlas[(size_t)out.parent[i]])) out.nested = false;
-    }
-    alloc_nodes(nB, out.blas);
-    {
-        // every instance owns the node range [blasRoot, blasRoot + blasNodeCount); each distinct range is renumbered
-        // on its own (root stays first).  Ranges that overlap without being equal cannot all be in walk order:
-        // the whole array then keeps the builder's numbering.
-        std::vector<std::pair<int64_t, int64_t>> ranges;
-        for (int64_t i = 0; i < nI; i++)
-            if (s->instances[i].blasNodeCount > 0) ranges.emplace_back((int64_t)s->instances[i].blasRoot, (int64_t)s->instances[i].blasRoot + s->instances[i].blasNodeCount);
-        std::sort(ranges.begin(), ranges.end());
-        ranges.erase(std::unique(ranges.begin(), ranges.end()), ranges.end());
-        bool disjoint = true;
-        for (size_t i = 1; i < ranges.size(); i++) if (ranges[i].first < ranges[i - 1].second) disjoint = false;
-        const size_t nBq = out.blas.size();
-        out.bparent.assign(nBq, -2); out.bnchild.assign(nBq, 0); out.bsubend.assign(nBq, 0); out.borig.assign(nBq, 0); out.bkind.assign(nBq, 0);
-        for (size_t j = 0; j < nBq; j++) out.borig[j] = (int32_t)j;
-        if (!disjoint)
-        {
-            perm.resize((size_t)nB);
-            for (size_t j = 0; j < perm.size(); j++) perm[j] = (int32_t)j;
-            pack_range(s->blasNodes, 0, nB, perm, out.blas);
-            out.blas_refit_ok = false;
-        }
-        else
-        {
-            // who owns each range: bit 0 a triangle mesh, bit 1 anything else
-            std::vector<uint8_t> rangeKind(ranges.size(), 0);
-            for (int64_t i = 0; i < nI; i++)
-            {
-                const hrt_instance& in = s->instances[i];
-                if (in.blasNodeCount <= 0) continue;
-                const auto it = std::lower_bound(ranges.begin(), ranges.end(), std::make_pair((int64_t)in.blasRoot, (int64_t)in.blasRoot + in.blasNodeCount));
-                rangeKind[(size_t)(it - ranges.begin())] |= in.type == HRT_BLAS_TRIMESH ? 1 : (in.type == HRT_BLAS_SPHERESET ? 2 : 4);
-            }
-            int64_t at = 0;
-            for (const auto& r : ranges)
-            {
-                for (; at < r.first; at++) { perm.assign(1, 0); pack_range(s->blasNodes, at, at + 1, perm, out.blas); }   // owned by no instance: never walked
-                const int32_t reach = walk_order(s->blasNodes, r.first, r.second, r.first, perm);
-                pack_range(s->blasNodes, r.first, r.second, perm, out.blas);
-                at = r.second;
-                // maintenance arrays for the BLAS of a triangle mesh (device refit after a vertex update, hrt_bvh.hpp)
-                const uint8_t kind = rangeKind[(size_t)(&r - ranges.data())];
-                if (kind != 1 && kind != 2) { if (kind != 0) out.blas_refit_ok = false; continue; }               // shared between a mesh and a sphere set, or of an unknown type
-                if (reach != (int32_t)(r.second - r.first)) { out.blas_refit_ok = false; continue; }              // unreachable nodes
-                for (int64_t k = r.first; k < r.second; k++) out.bkind[(size_t)k] = kind;
-                if (kind == 1) out.meshRanges.push_back(r);
-                out.max_range[kind] = std::max(out.max_range[kind], (int)(r.second - r.first));
-                auto cntq = [&](int64_t i) { return (int)((unsigned)__builtin_bit_cast(int, out.blas[(size_t)i].hi.w) >> 28); };
-                auto skipq = [&](int64_t i) { return __builtin_bit_cast(int, out.blas[(size_t)i].hi.w) & kEnd; };
-                for (int64_t k = r.first; k < r.second; k++) out.borig[(size_t)(r.first + perm[(size_t)(k - r.first)])] = (int32_t)k;
-                out.bparent[(size_t)r.first] = -1;
-                for (int64_t i = r.first; i < r.second; i++)
-                {
-                    const int sk = skipq(i);
-                    out.bsubend[(size_t)i] = (int32_t)(sk == kEnd ? r.second : sk);
-                    if (cntq(i) > 0) continue;
-                    int c = __builtin_bit_cast(int, out.blas[(size_t)i].lo.w) & kEnd;
-                    int steps = 0;
-                    while (c != kEnd && c != sk)
-                    {
-                        if (c <= i || c >= r.second || out.bparent[(size_t)c] != -2 || ++steps > 64) { out.blas_refit_ok = false; break; }
-                        out.bparent[(size_t)c] = (int32_t)i; out.bnchild[(size_t)i]++;
-                        c = skipq(c);
-                    }
-                }
-            }
-            for (; at < nB; at++) { perm.assign(1, 0); pack_range(s->blasNodes, at, at + 1, perm, out.blas); }
-        }
-        for (int64_t i = 0; i < nI; i++)
-        {
-            const hrt_instance& in = s->instances[i];
-            if (in.type == HRT_BLAS_SPHERESET && in.blasNodeCount > 0) out.sphereInst.push_back((int32_t)i);
-            if (in.type != HRT_BLAS_TRIMESH || in.blasNodeCount <= 0) continue;
-            out.meshInst.push_back((int32_t)i);
-            // region of triPrimIdx the leaves of this BLAS point into (the builder appends it behind the item list, Scene.cs:439-440)
-            int64_t lo = INT64_MAX, hi = -1, sum = 0;
-            for (int64_t k = in.blasRoot; k < (int64_t)in.blasRoot + in.blasNodeCount; k++)
-            {
-                const hrt_bvh_node& b = s->blasNodes[k];
-                if (b.count <= 0) continue;
-                lo = std::min<int64_t>(lo, b.first); hi = std::max<int64_t>(hi, (int64_t)b.first + b.count); sum += b.count;
-            }
-            const int64_t n = in.primIndexCount;
-            MeshJob J; J.inst = (int)i; J.root = in.blasRoot; J.nodeCap = in.blasNodeCount; J.leafBase = (int)lo; J.n = (int)n; J.itemFirst = in.primIndexFirst;
-            const bool items_ok = n > 0 && in.primIndexFirst >= 0 && (int64_t)in.primIndexFirst + n <= nTP;
-            const bool region_ok = hi - lo == n && sum == n && (lo >= (int64_t)in.primIndexFirst + n || hi <= in.primIndexFirst);
-            if (!items_ok || !region_ok || 2 * ((n + 13) / 14) - 1 > in.blasNodeCount) out.blas_rebuild_ok = false;
-            out.meshJobs.push_back(J);
-        }
-        {   // two meshes must not share a node range or a leaf region
-            std::vector<std::pair<int, int>> byRoot, byLeaf;
-            for (const MeshJob& J : out.meshJobs) { byRoot.emplace_back(J.root, J.nodeCap); byLeaf.emplace_back(J.leafBase, J.n); }
-            std::sort(byRoot.begin(), byRoot.end()); std::sort(byLeaf.begin(), byLeaf.end());
-            for (size_t k = 1; k < byRoot.size(); k++)
-                if (byRoot[k].first < byRoot[k - 1].first + byRoot[k - 1].second || byLeaf[k].first < byLeaf[k - 1].first + byLeaf[k - 1].second) out.blas_rebuild_ok = false;
-        }
-    }
-    if (nT == 0)
-    {   // reference semantics of the zeroed 1-element TLAS: node 0 has count 0, left 0 -> loops forever on a hit;
-        // its bounds are all zero so only rays through the origin would.  We end the walk instead.
-    }
-    out.finst.resize((size_t)std::max<int64_t>(nTI, 1));
-    std::memset(out.finst.data(), 0, out.finst.size() * sizeof(FInst));
-    for (int64_t i = 0; i < nTI; i++)
-    {
-        int ii = s->tlasInstanceIndices[i];
-        const hrt_instance& in = s->instances[ii];
-        const bool ident = is_identity(in.objectToWorld) && is_identity(in.worldToObject) && in.uniformScale == 1.0f;
-        const bool sph = in.type == HRT_BLAS_SPHERESET;
-        FInst f;
-        bool fast = false;
-        if (sph && ident && in.blasNodeCount >= 1)
-        {
-            const hrt_bvh_node& root = s->blasNodes[in.blasRoot];
-            int64_t end = (int64_t)in.blasRoot + in.blasNodeCount;
-            if (root.count == 1 && (root.skipIndex == -1 || root.skipIndex >= end))
-            {
-                int sid = s->spherePrimIdx[root.first];
-                const hrt_sphere& sp = s->spheres[sid];
-                f.a = mkf4(root.boundsMin.X, root.boundsMin.Y, root.boundsMin.Z, bits_f(FI_FAST_SPHERE | FI_IDENTITY | FI_SPHERESET));
-                f.b = mkf4(root.boundsMax.X, root.boundsMax.Y, root.boundsMax.Z, bits_f(sid));
-                f.c = mkf4(sp.center.X, sp.center.Y, sp.center.Z, sp.radius);
-                fast = true;
-            }
-        }
-        if (!fast)
-        {
-            out.feat |= 1;
-            float scale = in.uniformScale > 0.f ? in.uniformScale : 1.f;
-            f.a = mkf4(0.f, 0.f, 0.f, bits_f((ident ? FI_IDENTITY : 0) | (sph ? FI_SPHERESET : 0)));
-            f.b = mkf4(0.f, 0.f, 0.f, bits_f(ii));
-            f.c = mkf4(bits_f(in.blasRoot), bits_f(in.blasRoot + in.blasNodeCount), scale, 0.f);
-        }
-        out.finst[(size_t)i] = f;
-        // BOTH corners of the own box: a negative radius inverts it (max < min), and the slab test reads that as the mirror image
-        auto within = [](float v, float lo, float hi) { return v >= lo && v <= hi; };      // false with a NaN
-        if (fast && !(within(f.a.x, in.worldBoundsMin.X, in.worldBoundsMax.X) && within(f.b.x, in.worldBoundsMin.X, in.worldBoundsMax.X) &&
-                      within(f.a.y, in.worldBoundsMin.Y, in.worldBoundsMax.Y) && within(f.b.y, in.worldBoundsMin.Y, in.worldBoundsMax.Y) &&
-                      within(f.a.z, in.worldBoundsMin.Z, in.worldBoundsMax.Z) && within(f.b.z, in.worldBoundsMin.Z, in.worldBoundsMax.Z))) out.own_in_world = false;
-    }
-    out.ftri.resize((size_t)std::max<int64_t>(nTP, 1));
-    std::memset(out.ftri.data(), 0, out.ftri.size() * sizeof(FTri));
-    const int64_t texLen = nTxI > 0 ? nTxI : 1;
-    for (int64_t j = 0; j < nTP; j++)
-    {
-        int ti = s->triPrimIdx[j];
-        const hrt_mesh_tri& t = s->meshTris[ti];
-        const hrt_float3 &a = s->meshPositions[t.i0], &b = s->meshPositions[t.i1], &c = s->meshPositions[t.i2];
-        int mi = s->triMatIndex[ti];
-        static const hrt_material kZeroMaterial = {};
-        const hrt_material& m = nM > 0 ? s->materials[mi] : kZeroMaterial;
-        bool dmap = m.HasDiffuseMap != 0 && m.DiffuseTexIndex >= 0 && m.DiffuseTexIndex < texLen;
-        bool amap = m.HasAlphaMap != 0 && m.AlphaTexIndex >= 0 && m.AlphaTexIndex < texLen;
-        bool rejects_opaque = 1.0f < m.AlphaCutoff;
-        int fl = ((dmap || amap || rejects_opaque) ? FT_TEXTURED : 0) | (m.TwoSided != 0 ? FT_TWOSIDED : 0);
-        if (amap || rejects_opaque) out.feat |= 2;          // the walk itself must evaluate alpha (diffuse-only maps are resolved after it)
-        FTri& o = out.ftri[(size_t)j];
-        o.v0 = mkf4(a.X, a.Y, a.Z, bits_f(ti));
-        o.v1 = mkf4(b.X, b.Y, b.Z, bits_f(mi));
-        o.v2 = mkf4(c.X, c.Y, c.Z, bits_f(fl));
-    }
-    // ---- sphere-instance scenes: instance records inlined into the TLAS node stream (hrt_walker.hpp).  A leaf is followed by
-    // one record per instance holding the box of its one-node BLAS; the walker treats them as nodes (count field 15), so the
-    // instance box tests ride the node steps and their lookahead instead of costing a leaf step each.
-    out.tlasX.assign(1, NodeQ{});
-    bool leavesFit = true;                   // count code 15 marks an instance record in this stream: a leaf of 15 instances cannot be told from one
-    for (int64_t i = 0; i < nT; i++) if (((unsigned)__builtin_bit_cast(int, out.tlas[(size_t)i].hi.w) >> 28) > 14u) leavesFit = false;
-    if (out.ok && out.feat == 0 && reachableT > 0 && nT + nTI < kEnd && leavesFit)
-    {
-        std::vector<int32_t> nidx((size_t)nT);
-        int32_t at = 0;
-        auto cnt_of = [&](int64_t i) { return (int)((unsigned)__builtin_bit_cast(int, out.tlas[(size_t)i].hi.w) >> 28); };
-        for (int64_t i = 0; i < nT; i++) { nidx[(size_t)i] = at; at += 1 + cnt_of(i); }
-        auto remap = [&](int v) { return v == kEnd ? kEnd : (int)nidx[(size_t)v]; };
-        out.tlasX.assign((size_t)at, NodeQ{});
-        for (int64_t i = 0; i < nT; i++)
-        {
-            const NodeQ& q = out.tlas[(size_t)i];
-            const int c = cnt_of(i), link = __builtin_bit_cast(int, q.lo.w), sk = remap(__builtin_bit_cast(int, q.hi.w) & kEnd);
-            NodeQ& o = out.tlasX[(size_t)nidx[(size_t)i]];
-            o = q;
-            o.hi.w = bits_f(sk | (int)((unsigned)c << 28));
-            if (c == 0) { o.lo.w = bits_f(remap(link & kEnd)); continue; }
-            for (int j = 0; j < c; j++)
-            {
-                const FInst& f = out.finst[(size_t)(link + j)];
-                NodeQ& r = out.tlasX[(size_t)(nidx[(size_t)i] + 1 + j)];
-                r.lo = mkf4(f.a.x, f.a.y, f.a.z, bits_f(link + j));
-                const int next = (j + 1 < c) ? nidx[(size_t)i] + 2 + j : sk;
-                r.hi = mkf4(f.b.x, f.b.y, f.b.z, bits_f(next | (int)(15u << 28)));
-            }
-        }
-        out.n_tlasX = at;
-    }
-
-    // fast-sphere instances: own box inside the box of the leaf that lists them
-    for (int64_t i = 0; out.nested && i < nT; i++)
-    {
-        const NodeQ& q = out.tlas[(size_t)i];
-        const int cnt = (int)((unsigned)__builtin_bit_cast(int, q.hi.w) >> 28), first = __builtin_bit_cast(int, q.lo.w);
-        if (cnt == 0 || (int32_t)i >= reachableT) continue;
-        for (int j = 0; j < cnt; j++)
-        {
-            if ((int64_t)first + j < 0 || (int64_t)first + j >= nTI) { out.nested = false; break; }
-            const FInst& f = out.finst[(size_t)(first + j)];
-            if (!(__builtin_bit_cast(int, f.a.w) & FI_FAST_SPHERE)) continue;
-            // both corners of the own box (a negative radius inverts it, and the slab test reads that as the mirror image)
-            auto within = [](float v, float lo, float hi) { return v >= lo && v <= hi; };
-            if (!(within(f.a.x, q.lo.x, q.hi.x) && within(f.b.x, q.lo.x, q.hi.x) && within(f.a.y, q.lo.y, q.hi.y) && within(f.b.y, q.lo.y, q.hi.y) &&
-                  within(f.a.z, q.lo.z, q.hi.z) && within(f.b.z, q.lo.z, q.hi.z))) { out.nested = false; break; }
-        }
-    }
-    if (!out.nested) out.inst_once = false;
-    // TracerFlat: the reachable TLAS leaves in walk order, for scenes made of fast-sphere instances only
-    out.flat.assign(1, NodeQ{});
-    if (out.ok && out.feat == 0 && reachableT > 0 && out.nested)
-    {
-        std::vector<NodeQ> leaves;
-        for (int32_t i = 0; i < reachableT; i++)
-            if (((unsigned)__builtin_bit_cast(int, out.tlas[(size_t)i].hi.w) >> 28) != 0) leaves.push_back(out.tlas[(size_t)i]);
-        if (!leaves.empty() && (int)leaves.size() <= kFlatMaxLeaves) out.flat = leaves;
-        else out.flat.clear(), out.flat.assign(1, NodeQ{});
-        out.n_flat = (!leaves.empty() && (int)leaves.size() <= kFlatMaxLeaves) ? (int)leaves.size() : 0;
-    }
-    return "";
-}
-
 // copies the strips `owner` renders (rows [row_begin,row_end), strips s % strip_n == strip_i) of one per-pixel array
 // from src to dst (same global indexing on both sides) on `stream`: device -> host gather, or device -> device exchange
 template <class T>
@@ -1303,11 +707,6 @@ int gather_rows(hrt_ctx* c, DeviceState& d, T* host, const T* devp, int width)
 // The path-trace launch of one device, either as the one-pixel-per-lane megakernel or as the
 // streamed pipeline of hrt_wavefront.hpp (default).
 // ---------------------------------------------------------------------------------------
-// Organisation of the path-trace launch when the caller does not force one: scenes whose whole BVH
-// is a few cache lines (the reference's default scene, BASELINE config 2) spend their time in ReSTIR
-// arithmetic, not in the walk -- streaming path state through HBM only adds traffic there (measured:
-// 2.8 ms fused vs 5.3 ms streamed on config 2; 158 ms vs 33 ms on config 3).
-constexpr long long kSmallSceneNodes = 256;
 constexpr long long kWfMaxPaths = 1ll << 25;      // paths resident per sample batch (320 B of workspace each)
 
 // workspace of batch lane `lane` (0 / 1); growing one drains the device first (frames of earlier calls may still use it)
@@ -1659,15 +1058,6 @@ int run_path_stage(hrt_ctx* c, DeviceState& d, const TR& tr, const FrameK& k, co
     if (nLanes >= 2 && batch > 1 && (batch - 1) % nLanes != 0) HIPCHK(c, hipStreamWaitEvent(d.stream, d.evLane[(batch - 1) % nLanes][2], 0));
     return HRT_OK;
 }
-
-struct SahTopology { std::vector<int32_t> order; std::vector<NodeQ> nodes; std::vector<int> parent, nchild; int leaves = 0; };
-void host_sah_topology(const std::vector<hrt_instance>& inst, SahTopology& out);
-constexpr int64_t kAnyTreeMinInstances = 256;       // scenes of fewer instances keep the uploaded tree alone (second tree: see build_second_tree)
-#ifndef HRT_SAH_MAX_LOG2            // A/B (300 001 instances: LBVH topology 12.3 ms per frame and 0.29 s per upload, SAH 11.5 ms and 0.38 s)
-#define HRT_SAH_MAX_LOG2 21
-#endif
-constexpr int64_t kHostSahMaxInstances = (int64_t)1 << HRT_SAH_MAX_LOG2;
-int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, int64_t nSlots, bool instOnce, const SahTopology* pre = nullptr, const hrt_instance* hostInst = nullptr);       // defined with the scene-update code below
 
 // ---------------------------------------------------------------------------------------
 // Ray queries (hrt_trace_rays, kernels in hrt_query.hpp).  Rays are walked in chunks of at most kQueryChunk, so the memory a query
@@ -2069,829 +1459,6 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(c, "hrt_synchronize"); }
-
-int hrt_scene_upload(hrt_ctx* c, const hrt_scene_desc* s)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
-    c->frame_serial++;                         // ... and denoised planes no longer belong to what is on the device
-    c->dev[0].dt_valid = false;                // ... nor does the temporal denoiser's history
-    if (!s) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: scene is NULL");
-    const void* src[15] = {s->tlasNodes, s->tlasInstanceIndices, s->instances, s->blasNodes, s->spherePrimIdx, s->spheres,
-                           s->triPrimIdx, s->meshPositions, s->meshTris, s->meshTexcoords, s->meshTriUVs, s->triMatIndex,
-                           s->materials, s->texels, s->texInfos};
-    const int64_t cnt[15] = {s->n_tlasNodes, s->n_tlasInstanceIndices, s->n_instances, s->n_blasNodes, s->n_spherePrimIdx, s->n_spheres,
-                             s->n_triPrimIdx, s->n_meshPositions, s->n_meshTris, s->n_meshTexcoords, s->n_meshTriUVs, s->n_triMatIndex,
-                             s->n_materials, s->n_texels, s->n_texInfos};
-    for (int i = 0; i < 15; i++)
-        if (cnt[i] < 0 || (cnt[i] > 0 && !src[i])) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: array " + std::to_string(i) + " has a count but no pointer");
-    PackedHost ph;
-    {
-        std::string verr = validate_and_pack(s, ph);
-        if (!verr.empty()) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_upload: " + verr);
-    }
-    int rc = hrt_synchronize(c, nullptr);
-    if (rc != HRT_OK) return rc;
-    c->scene_ready = false;
-    c->packed_ok = ph.ok;
-    c->packed_feat = (ph.feat & 2) ? 3 : (ph.feat & 1);
-    c->small_scene = (s->n_tlasNodes + s->n_blasNodes) <= kSmallSceneNodes;
-    c->flat_leaves = ph.n_flat;
-    c->own_in_world = ph.own_in_world;
-    c->refit_ok = ph.refit_ok && ph.ok;
-    c->feat_alpha = (ph.feat & 2) != 0;
-    c->n_inst = s->n_instances; c->n_tlas = s->n_tlasNodes; c->n_slots = s->n_tlasInstanceIndices; c->n_blas = s->n_blasNodes;
-    c->tlas_leaves = ph.reach_leaves;
-    c->tlas_on_device = false;
-    c->blas_refit_ok = ph.blas_refit_ok && ph.ok;
-    c->blas_rebuild_ok = c->blas_refit_ok && ph.blas_rebuild_ok;
-    c->mesh_jobs = ph.meshJobs;
-    c->max_mesh_items = 0;
-    for (const MeshJob& J : ph.meshJobs) c->max_mesh_items = std::max(c->max_mesh_items, J.n);
-    c->n_positions = s->n_meshPositions; c->n_spheres = s->n_spheres;
-    for (int i = 0; i < 15; i++) c->scene_count[i] = cnt[i];
-    // room for a TLAS rebuilt on the device over all instances (leaves of two: hrt_bvh.hpp)
-    const int64_t capT = std::max<int64_t>(std::max<int64_t>(s->n_tlasNodes, 2 * s->n_instances - 1), 1);
-    const int64_t capTI = std::max<int64_t>(std::max<int64_t>(s->n_tlasInstanceIndices, s->n_instances), 1);
-    hrt_bvh_node emptyTlas; std::memset(&emptyTlas, 0, sizeof(emptyTlas));
-    emptyTlas.left = emptyTlas.right = emptyTlas.first = emptyTlas.skipIndex = -1;   // an empty TLAS ends the walk at once
-    // topology of the second tree (many-sphere scenes): a function of the instances alone, computed once for all devices
-    SahTopology sahOnce; bool haveSah = false;
-    if (ph.ok && ph.feat == 0 && s->n_instances >= kAnyTreeMinInstances && ph.n_tlasX > 0 && ph.inst_once && s->n_tlasInstanceIndices == s->n_instances &&
-        ph.own_in_world && s->n_instances <= kHostSahMaxInstances && s->n_instances > 2)
-    {
-        const std::vector<hrt_instance> inst(s->instances, s->instances + s->n_instances);
-        host_sah_topology(inst, sahOnce);
-        haveSah = true;
-    }
-    TreeletsHost tlh;
-    if (ph.ok && (ph.feat & 1) && ph.blas_refit_ok && !ph.meshRanges.empty()) build_treelets(ph.blas, ph.bsubend, ph.meshRanges, g_treelet_limits, tlh);
-    for (DeviceState& d : c->dev)
-    {
-        HIPCHK(c, hipSetDevice(d.device_id));
-        free_scene(d);                                  // UploadAll disposes + reallocates all 15 (Scene.cs:260-278)
-        for (int i = 0; i < 15; i++)
-        {
-            int64_t n = cnt[i] > 0 ? cnt[i] : 1;       // AllocateOrEmpty: empty -> 1 zeroed element
-            size_t bytes = (size_t)n * kSceneElem[i];
-            const size_t room = i == 0 ? (size_t)capT * kSceneElem[0] : (i == 1 ? (size_t)capTI * kSceneElem[1] : bytes);
-            HIPCHK(c, hipMalloc(&d.scene[i], std::max(bytes, room)));
-            if (cnt[i] > 0) HIPCHK(c, hipMemcpyAsync(d.scene[i], src[i], bytes, hipMemcpyHostToDevice, d.stream));
-            else if (i == 0) HIPCHK(c, hipMemcpyAsync(d.scene[i], &emptyTlas, bytes, hipMemcpyHostToDevice, d.stream));
-            else HIPCHK(c, hipMemsetAsync(d.scene[i], 0, bytes, d.stream));
-        }
-        DScene& S = d.dscene;
-        S.tlasNodes = (const hrt_bvh_node*)d.scene[0]; S.tlasInst = (const int32_t*)d.scene[1];
-        S.instances = (const hrt_instance*)d.scene[2]; S.blasNodes = (const hrt_bvh_node*)d.scene[3];
-        S.spherePrimIdx = (const int32_t*)d.scene[4]; S.spheres = (const hrt_sphere*)d.scene[5];
-        S.triPrimIdx = (const int32_t*)d.scene[6]; S.meshPositions = (const hrt_float3*)d.scene[7];
-        S.meshTris = (const hrt_mesh_tri*)d.scene[8]; S.meshTexcoords = (const hrt_float2*)d.scene[9];
-        S.meshTriUVs = (const hrt_mesh_tri_uv*)d.scene[10]; S.triMatIndex = (const int32_t*)d.scene[11];
-        S.materials = (const hrt_material*)d.scene[12]; S.texels = (const hrt_rgba32*)d.scene[13];
-        S.texInfos = (const hrt_tex_info*)d.scene[14];
-        S.n_texInfos = (int32_t)(cnt[14] > 0 ? cnt[14] : 1);
-        // device-private repack (TracerPacked)
-        const void* psrc[7] = {ph.tlas.data(), ph.finst.data(), ph.blas.data(), ph.ftri.data(), ph.flat.data(), nullptr, ph.tlasX.data()};       // slot 5 unused
-        const size_t pbytes[7] = {ph.tlas.size() * sizeof(NodeQ), ph.finst.size() * sizeof(FInst), ph.blas.size() * sizeof(NodeQ), ph.ftri.size() * sizeof(FTri),
-                                  ph.flat.size() * sizeof(NodeQ), 0, ph.tlasX.size() * sizeof(NodeQ)};
-        const size_t proom[7] = {(size_t)capT * sizeof(NodeQ), (size_t)capTI * sizeof(FInst), 0, 0, (size_t)kFlatMaxLeaves * sizeof(NodeQ), 0,
-                                 (size_t)(capT + capTI) * sizeof(NodeQ)};
-        for (int i = 0; i < 7; i++)
-        {
-            if (!psrc[i]) continue;
-            HIPCHK(c, hipMalloc(&d.packed[i], std::max(pbytes[i], proom[i])));
-            HIPCHK(c, hipMemcpyAsync(d.packed[i], psrc[i], pbytes[i], hipMemcpyHostToDevice, d.stream));
-        }
-        {   // maintenance arrays of the device-side TLAS update
-            const size_t scanTmp = (tlas_scan_temp_bytes((int)capT) + 255) & ~(size_t)255, nPart = (size_t)(capT + 255) / 256;
-            const size_t ab[10] = {(size_t)capT * 4, (size_t)capT * 4, (size_t)capT * 4, (size_t)capT * 8, (size_t)capT * 8, (size_t)capT * 4, 16, 16, (size_t)capT * 4,
-                                   scanTmp + 3 * nPart * 4};
-            for (int i = 0; i < 10; i++) { HIPCHK(c, hipMalloc(&d.tlaux[i], ab[i])); HIPCHK(c, hipMemsetAsync(d.tlaux[i], 0, ab[i], d.stream)); }
-            if (!ph.parent.empty())
-            {
-                HIPCHK(c, hipMemcpyAsync(d.tlaux[0], ph.parent.data(), std::min(ph.parent.size(), (size_t)capT) * 4, hipMemcpyHostToDevice, d.stream));
-                HIPCHK(c, hipMemcpyAsync(d.tlaux[1], ph.nchild.data(), std::min(ph.nchild.size(), (size_t)capT) * 4, hipMemcpyHostToDevice, d.stream));
-            }
-            TlasDevice& T = d.tl;
-            T = TlasDevice{};
-            T.tlasNodes = (hrt_bvh_node*)d.scene[0]; T.tlasInst = (int32_t*)d.scene[1]; T.instances = (hrt_instance*)d.scene[2];
-            T.blasNodes = (const hrt_bvh_node*)d.scene[3]; T.spherePrimIdx = (const int32_t*)d.scene[4]; T.spheres = (const hrt_sphere*)d.scene[5];
-            T.tlas = (NodeQ*)d.packed[0]; T.finst = (FInst*)d.packed[1]; T.tlasX = (NodeQ*)d.packed[6]; T.flat = (NodeQ*)d.packed[4];
-            T.parent = (int*)d.tlaux[0]; T.nchild = (int*)d.tlaux[1]; T.arrive = (int*)d.tlaux[2]; T.scanIn = (unsigned long long*)d.tlaux[3]; T.scanOut = (unsigned long long*)d.tlaux[4];
-            T.scanTmp = d.tlaux[9]; T.scanTmpBytes = scanTmp; T.costPartial = (float*)((char*)d.tlaux[9] + scanTmp);
-            T.directMax = 63;                                   // walk order; apply_update rebuilds a tree that fails refit_ok first
-            T.sa = (float*)d.tlaux[5]; T.flags = (int*)d.tlaux[6]; T.cost = (float*)d.tlaux[7]; T.saBase = (float*)d.tlaux[8];
-            T.nI = (int)s->n_instances; T.nT = (int)s->n_tlasNodes; T.nTI = (int)s->n_tlasInstanceIndices;
-            if ((!ph.meshInst.empty() || !ph.sphereInst.empty()) && ph.blas_refit_ok)
-            {
-                const size_t nBq = ph.blas.size();
-                static const int32_t none = 0;
-                const void* bsrc[12] = {ph.bparent.data(), ph.bnchild.data(), ph.bsubend.data(), ph.borig.data(), nullptr,
-                                        ph.meshInst.empty() ? &none : ph.meshInst.data(), ph.bkind.data(), ph.sphereInst.empty() ? &none : ph.sphereInst.data(),
-                                        nullptr, nullptr, nullptr, nullptr};
-                const size_t bb[12] = {nBq * 4, nBq * 4, nBq * 4, nBq * 4, nBq * 4, std::max<size_t>(ph.meshInst.size(), 1) * 4, nBq * 4, std::max<size_t>(ph.sphereInst.size(), 1) * 4,
-                                       nBq * 4, nBq * 4, ((nBq + 255) / 256) * 8, 16};
-                for (int i = 0; i < 12; i++)
-                {
-                    HIPCHK(c, hipMalloc(&d.blaux[i], bb[i]));
-                    if (bsrc[i]) HIPCHK(c, hipMemcpyAsync(d.blaux[i], bsrc[i], bb[i], hipMemcpyHostToDevice, d.stream));
-                    else HIPCHK(c, hipMemsetAsync(d.blaux[i], 0, bb[i], d.stream));
-                }
-                BlasDevice& B = d.bl;
-                B.blasNodes = (hrt_bvh_node*)d.scene[3]; B.triPrimIdx = (const int32_t*)d.scene[6]; B.meshTris = (const hrt_mesh_tri*)d.scene[8];
-                B.triPrimIdxW = (int32_t*)d.scene[6]; B.triMatIndex = (const int32_t*)d.scene[11]; B.materials = (const hrt_material*)d.scene[12];
-                B.nMaterials = (int)s->n_materials; B.texLen = (int)(s->n_texInfos > 0 ? s->n_texInfos : 1);
-                B.spherePrimIdx = (const int32_t*)d.scene[4]; B.spheres = (const hrt_sphere*)d.scene[5]; B.kind = (int*)d.blaux[6];
-                B.sa = (float*)d.blaux[8]; B.saBase = (float*)d.blaux[9]; B.growPartial = (float*)d.blaux[10]; B.grow = (float*)d.blaux[11];
-                B.positions = (hrt_float3*)d.scene[7]; B.blas = (NodeQ*)d.packed[2]; B.ftri = (FTri*)d.packed[3];
-                B.parent = (int*)d.blaux[0]; B.nchild = (int*)d.blaux[1]; B.subend = (int*)d.blaux[2]; B.orig = (int*)d.blaux[3]; B.arrive = (int*)d.blaux[4];
-                B.nB = (int)s->n_blasNodes; B.nSlots = (int)s->n_triPrimIdx; B.directMax = 7;   // leaves cost up to four triangle records each: 7 / 15 / 31 / 63 measured 0.47 / 0.50 / 0.52 / 0.56 ms for the refit of a 524 k-node BLAS
-                B.maxRange[0] = 0; B.maxRange[1] = ph.max_range[1]; B.maxRange[2] = ph.max_range[2];
-                d.n_sphere_inst = (int)ph.sphereInst.size();
-                d.n_mesh_inst = (int)ph.meshInst.size();
-            }
-            T.capT = (int)capT; T.capTI = (int)capTI; T.flatMax = kFlatMaxLeaves;
-        }
-        d.dpacked.tlas = (const NodeQ*)d.packed[0]; d.dpacked.finst = (const FInst*)d.packed[1];
-        d.dpacked.blas = (const NodeQ*)d.packed[2]; d.dpacked.ftri = (const FTri*)d.packed[3];
-        d.dpacked.nTlas = (int)ph.tlas.size();
-        d.dpacked.tlasX = ph.n_tlasX > 0 ? (const NodeQ*)d.packed[6] : nullptr; d.dpacked.nTlasX = ph.n_tlasX;
-        {   // triangle records per leaf step of the walker: three where leaves of three outnumber the fuller ones, else two (hrt_walker.hpp)
-            size_t n3 = 0, n4 = 0;
-            for (const NodeQ& q : ph.blas)
-            {
-                const unsigned cnt = (unsigned)__builtin_bit_cast(int, q.hi.w) >> 28;
-                if (cnt == 3) n3++; else if (cnt >= 4) n4++;
-            }
-            d.dpacked.leafTris = n3 > n4 ? 3 : 2;
-        }
-        // treelets of the big triangle-mesh BLASes: what the LDS-staged walker of production frames walks (hrt_walker_tl.hpp)
-        if (ph.ok && (ph.feat & 1) && ph.blas_refit_ok && !ph.meshRanges.empty() && !tlh.tl.empty())
-        {
-            const void* tsrc[3] = {tlh.red.data(), tlh.tl.data(), tlh.redOfRoot.data()};
-            const size_t tbytes[3] = {tlh.red.size() * sizeof(NodeQ), tlh.tl.size() * sizeof(Treelet), tlh.redOfRoot.size() * sizeof(int32_t)};
-            for (int i = 0; i < 3; i++)
-            {
-                HIPCHK(c, hipMalloc(&d.tlmem[i], tbytes[i]));
-                HIPCHK(c, hipMemcpyAsync(d.tlmem[i], tsrc[i], tbytes[i], hipMemcpyHostToDevice, d.stream));
-            }
-            d.dtl.red = (const NodeQ*)d.tlmem[0]; d.dtl.tl = (const Treelet*)d.tlmem[1]; d.dtl.redOfRoot = (const int*)d.tlmem[2];
-            d.dtl.nTl = (int)tlh.tl.size(); d.dtl.nRed = (int)tlh.red.size();
-            d.dtl.redLds = (int)std::min<size_t>(tlh.red.size(), (size_t)kTlRedLdsMax);
-            d.dtl.tlBytesMax = (tlh.tlBytesMax + 15) & ~15;
-            const int histBins = d.dtl.nTl <= kTlHistLds ? d.dtl.nTl : 0;
-            d.tl_ok = tl_shared_bytes(d.dtl.tlBytesMax, d.dtl.redLds, histBins) <= (size_t)d.max_lds;
-        }
-        HIPCHK(c, hipStreamSynchronize(d.stream));      // host arrays are only borrowed for the duration of the call
-        if (int rcB = build_second_tree(c, d, s->tlasInstanceIndices, s->n_tlasInstanceIndices, ph.inst_once, haveSah ? &sahOnce : nullptr, s->instances))
-        {   // the second tree is an accelerator, not part of the scene: without memory for it the walks use the uploaded tree
-            if (rcB != HRT_ERR_OUT_OF_MEMORY) return rcB;
-            (void)hipGetLastError();
-            for (int i = 0; i < 18; i++) { if (d.tl2mem[i]) (void)hipFree(d.tl2mem[i]); d.tl2mem[i] = nullptr; }
-            d.tl2 = TlasDevice{}; d.any_ok = false; d.any_built = false; d.ordX = d.ordP = 0;
-            c->err.clear();
-        }
-    }
-    c->scene_ready = true;
-    return HRT_OK;
-}
-catch (...) { return on_exception(c, "hrt_scene_upload"); }
-
-namespace {
-
-constexpr float kAutoRebuildGrowth = 1.5f;     // HRT_REBUILD_AUTO: rebuild when the node boxes grew to this multiple of their built area (geometric mean)
-
-int ensure_lbvh_scratch(hrt_ctx* c, DeviceState& d)
-{
-    if (d.tlscratch) return HRT_OK;
-    TlasDevice& T = d.tl;
-    const size_t n = (size_t)std::max(std::max(T.nI, c->max_mesh_items), 1);
-    const size_t L = n + 1;                                                                                   // Karras' tree over the single items
-    const size_t sortBytes = tlas_sort_temp_bytes((int)n), iscanBytes = tlas_iscan_temp_bytes((int)n + 1);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t total = 3 * up(n * 4) + 5 * up(L * 4) + up(6 * 4) + up(sortBytes) + 2 * up((n + 1) * 4) + up(16 * 4) + up(iscanBytes);
-    HIPCHK(c, hipMalloc(&d.tlscratch, total));
-    char* p = (char*)d.tlscratch;
-    auto take = [&](size_t b) { char* r = p; p += up(b); return (void*)r; };
-    T.keys = (unsigned*)take(n * 4); T.keysSorted = (unsigned*)take(n * 4); T.vals = (int*)take(n * 4);
-    T.rngA = (int*)take(L * 4); T.rngB = (int*)take(L * 4); T.split = (int*)take(L * 4); T.parInt = (int*)take(L * 4);
-    T.parLeaf = (int*)take(L * 4);
-    T.cboundsKey = (unsigned*)take(6 * 4);
-    T.lstart = (int*)take((n + 1) * 4); T.lsum = (int*)take((n + 1) * 4); T.leafCounts = (int*)take(16 * 4);
-    T.iscanTmp = take(iscanBytes); T.iscanTmpBytes = iscanBytes;
-    T.sortTmp = take(sortBytes); T.sortTmpBytes = sortBytes;
-    return HRT_OK;
-}
-
-// Scenes made of many fast-sphere instances (identity transform, one sphere): a second TLAS over the same instances (topology from
-// host_sah_topology below, or the LBVH of the scene updates for very many instances; everything else by the device kernels of the
-// scene updates), for the walks of the streamed pipeline (hrt_walker.hpp, ALT) and launch 1.  Any-hit walks and
-// the last bounce's hit-or-miss walk do not depend on the tree at all; a closest-hit walk depends on it only through the order
-// in which instances at exactly the same distance are met, which the walker detects and resolves on the uploaded tree.  The
-// reference's median split cuts such a scene into slabs when one instance dominates the bounds (the ground sphere of BASELINE
-// config 3: 103 node visits per ray against 50).  Needs the uploaded tree to list every instance exactly once (the
-// second tree is built over "the instances").  Scene updates refit it (refit_second_tree).
-
-// Topology of the second tree built on the HOST with a binned surface-area heuristic (16 bins on each axis over the box centres of
-// the range, the split of least area(left) * n(left) + area(right) * n(right); leaves of at most four instances; a range the bins cannot
-// split is halved), in the numbering the walkers want (walk order: a node's first child follows it).
-// Only WHICH instances share a subtree is decided here -- boxes, leaf-slot records, the inlined layout and the slack are the
-// device's (tlas_finish, tlas_inflate), exactly as for the LBVH the scene updates build.  Against that LBVH: 6-10 % fewer node
-// visits per ray on config 3 (tools/tree_order_model.py); the scene updates keep the LBVH, which is built in 0.3 ms, and so do
-// scenes of more than two million instances.
-constexpr int kSahLeaf = 4;       // instances per leaf at most (config 3, path stage + launch 1: 15.66 / 15.37 / 15.39 / 15.41 ms for 2 / 3 / 4 / 6)
-void host_sah_topology(const std::vector<hrt_instance>& inst, SahTopology& out)
-{
-    const int n = (int)inst.size();
-    constexpr int kBins = 16;
-    std::vector<float> cx((size_t)n), cy((size_t)n), cz((size_t)n);
-    for (int i = 0; i < n; i++)
-    {
-        cx[(size_t)i] = 0.5f * (inst[(size_t)i].worldBoundsMin.X + inst[(size_t)i].worldBoundsMax.X);
-        cy[(size_t)i] = 0.5f * (inst[(size_t)i].worldBoundsMin.Y + inst[(size_t)i].worldBoundsMax.Y);
-        cz[(size_t)i] = 0.5f * (inst[(size_t)i].worldBoundsMin.Z + inst[(size_t)i].worldBoundsMax.Z);
-        // (an infinite box is legal here; its centre only has to be a number the binning can convert to an integer)
-        if (!std::isfinite(cx[(size_t)i])) cx[(size_t)i] = 0.f;
-        if (!std::isfinite(cy[(size_t)i])) cy[(size_t)i] = 0.f;
-        if (!std::isfinite(cz[(size_t)i])) cz[(size_t)i] = 0.f;
-    }
-    const float* cen[3] = {cx.data(), cy.data(), cz.data()};
-    struct Box { float lo[3], hi[3]; };
-    auto grow = [&](Box& b, int i) {
-        const hrt_instance& r = inst[(size_t)i];
-        const float l[3] = {r.worldBoundsMin.X, r.worldBoundsMin.Y, r.worldBoundsMin.Z}, h[3] = {r.worldBoundsMax.X, r.worldBoundsMax.Y, r.worldBoundsMax.Z};
-        for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], l[a]); b.hi[a] = std::max(b.hi[a], h[a]); }
-    };
-    auto unite = [](Box& b, const Box& o) { for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], o.lo[a]); b.hi[a] = std::max(b.hi[a], o.hi[a]); } };
-    auto area = [](const Box& b) { const float x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2]; return x * y + y * z + z * x; };
-    const Box empty = {{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-    out.order.resize((size_t)n);
-    for (int i = 0; i < n; i++) out.order[(size_t)i] = i;
-    out.nodes.clear(); out.parent.clear(); out.nchild.clear(); out.leaves = 0;
-    struct Job { int a, b, parent; };
-    std::vector<Job> todo;
-    todo.push_back({0, n, -1});
-    while (!todo.empty())
-    {
-        const Job j = todo.back();
-        todo.pop_back();
-        const int idx = (int)out.nodes.size();
-        NodeQ q{};
-        out.parent.push_back(j.parent);
-        const int m = j.b - j.a;
-        if (m <= kSahLeaf)
-        {
-            q.lo.w = bits_f(j.a);
-            q.hi.w = bits_f((int)((unsigned)m << 28));           // the skip link comes with the subtree sizes, below
-            out.nodes.push_back(q); out.nchild.push_back(0); out.leaves++;
-            continue;
-        }
-        int32_t* it = out.order.data() + j.a;
-        int bestAxis = -1, bestK = 0; float bestCost = 0.f, bestLo = 0.f, bestScale = 0.f;
-        for (int a = 0; a < 3; a++)
-        {
-            float lo = FLT_MAX, hi = -FLT_MAX;
-            for (int i = 0; i < m; i++) { lo = std::min(lo, cen[a][it[i]]); hi = std::max(hi, cen[a][it[i]]); }
-            if (!(hi > lo) || !std::isfinite(hi - lo)) continue;
-            const float scale = (float)kBins / (hi - lo);
-            Box bb[kBins]; int cnt[kBins];
-            for (int k = 0; k < kBins; k++) { bb[k] = empty; cnt[k] = 0; }
-            for (int i = 0; i < m; i++)
-            {
-                const int k = std::min(kBins - 1, std::max(0, (int)((cen[a][it[i]] - lo) * scale)));
-                grow(bb[k], it[i]); cnt[k]++;
-            }
-            Box right[kBins]; int rcnt[kBins];
-            Box acc = empty; int c = 0;
-            for (int k = kBins - 1; k >= 1; k--) { unite(acc, bb[k]); c += cnt[k]; right[k] = acc; rcnt[k] = c; }
-            acc = empty; c = 0;
-            for (int k = 1; k < kBins; k++)
-            {
-                unite(acc, bb[k - 1]); c += cnt[k - 1];
-                if (c == 0 || rcnt[k] == 0) continue;
-                const float cost = area(acc) * (float)c + area(right[k]) * (float)rcnt[k];
-                if (std::isfinite(cost) && (bestAxis < 0 || cost < bestCost)) { bestAxis = a; bestK = k; bestCost = cost; bestLo = lo; bestScale = scale; }
-            }
-        }
-        int mid = m / 2;
-        if (bestAxis >= 0)
-        {
-            const float* ca = cen[bestAxis];
-            int32_t* p2 = std::partition(it, it + m, [&](int32_t i) { return std::min(kBins - 1, std::max(0, (int)((ca[i] - bestLo) * bestScale))) < bestK; });
-            const int left = (int)(p2 - it);
-            if (left > 0 && left < m) mid = left;
-        }
-        q.lo.w = bits_f(idx + 1);
-        out.nodes.push_back(q); out.nchild.push_back(2);
-        todo.push_back({j.a + mid, j.b, idx});       // popped second: the first child is the next node
-        todo.push_back({j.a, j.a + mid, idx});
-    }
-    // skip link = index + size of the subtree (walk order: children have larger indices than their parent)
-    const int nT = (int)out.nodes.size();
-    std::vector<int> size((size_t)nT, 1);
-    for (int i = nT - 1; i > 0; i--) size[(size_t)out.parent[(size_t)i]] += size[(size_t)i];
-    for (int i = 0; i < nT; i++)
-    {
-        const int end = i + size[(size_t)i];
-        const int w = __builtin_bit_cast(int, out.nodes[(size_t)i].hi.w);
-        out.nodes[(size_t)i].hi.w = bits_f((w & ~kEnd) | (end >= nT ? kEnd : end));
-    }
-}
-
-// The inlined second tree (TlasDevice::tlasX: nodes in walk order, every leaf followed by one record per instance) renumbered for the
-// rays whose direction has the signs `sign` (+1 / -1 per axis, 0: not known): at every inner node the child whose box centre comes first along such a ray,
-// on the axis that separates the two centres most, is walked first.  Same records, same subtree sizes; only the order of the two
-// subtrees under a node, and with it every link, changes.  Links are written as indices into the array of all eight copies
-// (`base` = where this copy starts); from[i] = the record of X that position i of the copy holds (a refit refreshes the boxes through it).
-// false: the array is not the binary tree in walk order it should be (nothing is used then).
-bool reorder_second_tree(const std::vector<NodeQ>& X, const int sign[3], int base, NodeQ* out, int* from, bool inlined)
-{
-    const int nX = (int)X.size();
-    auto w_ = [](float f) { return __builtin_bit_cast(int, f); };
-    auto f_ = [](int v) { return __builtin_bit_cast(float, v); };
-    auto cnt = [&](int i) { return (int)((unsigned)w_(X[(size_t)i].hi.w) >> 28); };
-    auto end = [&](int i) { const int sk = w_(X[(size_t)i].hi.w) & kEnd; return sk == kEnd ? nX : sk; };
-    std::vector<std::pair<int, int>> todo;                  // (record in X, its index in this numbering)
-    todo.emplace_back(0, 0);
-    int placed = 0;
-    while (!todo.empty())
-    {
-        const int src = todo.back().first, at = todo.back().second;
-        todo.pop_back();
-        if (src < 0 || src >= nX || at < 0 || at >= nX) return false;
-        const int size = end(src) - src;
-        if (size < 1 || at + size > nX) return false;
-        const int skip = at + size == nX ? kEnd : base + at + size;
-        const int c = cnt(src);
-        NodeQ q = X[(size_t)src];
-        if (c == 15) return false;                          // an instance record where a node should be
-        if (c > 0)
-        {
-            if (size != (inlined ? 1 + c : 1)) return false;
-            q.hi.w = f_(skip | (int)((unsigned)c << 28));
-            out[at] = q; from[at] = src;
-            placed += size;
-            if (!inlined) continue;                         // the plain node array: a leaf names its slots, no records follow
-            for (int j = 0; j < c; j++)
-            {
-                NodeQ r = X[(size_t)(src + 1 + j)];
-                if (cnt(src + 1 + j) != 15) return false;
-                r.hi.w = f_((j + 1 < c ? base + at + 2 + j : skip) | (int)(15u << 28));
-                out[at + 1 + j] = r; from[at + 1 + j] = src + 1 + j;
-            }
-            continue;
-        }
-        const int l = w_(q.lo.w) & kEnd;
-        if (l != src + 1 || l >= nX) return false;
-        const int r = end(l);
-        if (r >= nX || end(r) != end(src)) return false;    // exactly two children
-        const NodeQ &L = X[(size_t)l], &R = X[(size_t)r];
-        const float cl[3] = {0.5f * (L.lo.x + L.hi.x), 0.5f * (L.lo.y + L.hi.y), 0.5f * (L.lo.z + L.hi.z)};
-        const float cr[3] = {0.5f * (R.lo.x + R.hi.x), 0.5f * (R.lo.y + R.hi.y), 0.5f * (R.lo.z + R.hi.z)};
-        int ax = 0;
-        for (int a = 1; a < 3; a++) if (std::fabs(cl[a] - cr[a]) > std::fabs(cl[ax] - cr[ax])) ax = a;
-        // +1 / -1: the rays of this copy go that way along ax; 0: either way -- the builder's order stays (lower Morton code first)
-        const bool leftFirst = sign[ax] > 0 ? cl[ax] <= cr[ax] : (sign[ax] < 0 ? cl[ax] >= cr[ax] : true);
-        const int a = leftFirst ? l : r, b = leftFirst ? r : l;
-        q.lo.w = f_(base + at + 1);
-        q.hi.w = f_(skip);
-        out[at] = q; from[at] = src;
-        placed += 1;
-        todo.emplace_back(b, at + 1 + (end(a) - a));
-        todo.emplace_back(a, at + 1);
-    }
-    return placed == nX;
-}
-int build_second_tree(hrt_ctx* c, DeviceState& d, const int32_t* uploadedSlots, int64_t nSlots, bool instOnce, const SahTopology* pre, const hrt_instance* hostInst)
-{
-    d.any_ok = false; d.any_built = false;
-    // own_in_world: the second tree's leaf boxes are unions of the instances' worldBounds, and its exactness argument needs every instance's
-    // own box inside them (an instance whose BLAS the position-indexed builder put over another sphere, Scene.cs:386-395, breaks that)
-    if (!c->packed_ok || c->packed_feat != 0 || c->n_inst < kAnyTreeMinInstances || !d.dpacked.tlasX || !instOnce || nSlots != c->n_inst || !c->own_in_world) return HRT_OK;
-    int rc = ensure_lbvh_scratch(c, d);
-    if (rc != HRT_OK) return rc;
-    TlasDevice T = d.tl;                                        // inputs, capacities, temporaries and LBVH scratch are shared; outputs are its own
-    const size_t capT = (size_t)T.capT, capTI = (size_t)T.capTI;
-    const size_t bytes[14] = {capT * sizeof(hrt_bvh_node), capTI * 4, capT * sizeof(NodeQ), capTI * sizeof(FInst), (capT + capTI) * sizeof(NodeQ),
-                              (size_t)kFlatMaxLeaves * sizeof(NodeQ), capT * 4, capT * 4, capT * 4, capT * 8, capT * 8, capT * 4, capT * 4, 32};
-    for (int i = 0; i < 14; i++)
-    {
-        if (d.tl2mem[i]) { (void)hipFree(d.tl2mem[i]); d.tl2mem[i] = nullptr; }
-        HIPCHK(c, hipMalloc(&d.tl2mem[i], bytes[i]));
-        HIPCHK(c, hipMemsetAsync(d.tl2mem[i], 0, bytes[i], d.stream));
-    }
-    T.tlasNodes = (hrt_bvh_node*)d.tl2mem[0]; T.tlasInst = (int32_t*)d.tl2mem[1]; T.tlas = (NodeQ*)d.tl2mem[2]; T.finst = (FInst*)d.tl2mem[3];
-    T.tlasX = (NodeQ*)d.tl2mem[4]; T.flat = (NodeQ*)d.tl2mem[5]; T.parent = (int*)d.tl2mem[6]; T.nchild = (int*)d.tl2mem[7]; T.arrive = (int*)d.tl2mem[8];
-    T.scanIn = (unsigned long long*)d.tl2mem[9]; T.scanOut = (unsigned long long*)d.tl2mem[10]; T.sa = (float*)d.tl2mem[11]; T.saBase = (float*)d.tl2mem[12];
-    T.flags = (int*)d.tl2mem[13]; T.cost = (float*)((char*)d.tl2mem[13] + 16);
-    int leaves = 0;
-    // the instances as the host uploaded them (no copy back from the device when the caller still has them)
-    std::vector<hrt_instance> inst;
-    if (hostInst) inst.assign(hostInst, hostInst + c->n_inst);
-    else
-    {
-        inst.resize((size_t)c->n_inst);
-        HIPCHK(c, hipMemcpy(inst.data(), T.instances, inst.size() * sizeof(hrt_instance), hipMemcpyDeviceToHost));
-    }
-    if (c->n_inst <= kHostSahMaxInstances && c->n_inst > 2)
-    {
-        // the topology depends on the instances alone: the upload computes it once and hands it to every device
-        SahTopology own;
-        if (!pre) host_sah_topology(inst, own);
-        const SahTopology& sah = pre ? *pre : own;
-        T.nT = (int)sah.nodes.size(); T.nTI = (int)c->n_inst; leaves = sah.leaves;
-        if (T.nT > T.capT || T.nTI > T.capTI || T.nT != 2 * leaves - 1) return fail(c, HRT_ERR_HIP, "second tree: host topology does not fit");
-        HIPCHK(c, hipMemcpyAsync(T.tlas, sah.nodes.data(), sah.nodes.size() * sizeof(NodeQ), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, hipMemcpyAsync(T.tlasInst, sah.order.data(), sah.order.size() * 4, hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, hipMemcpyAsync(T.parent, sah.parent.data(), sah.parent.size() * 4, hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, hipMemcpyAsync(T.nchild, sah.nchild.data(), sah.nchild.size() * 4, hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, hipStreamSynchronize(d.stream));              // the vectors go out of scope
-    }
-    else
-        HIPCHK(c, tlas_rebuild_topology(T, d.stream, &leaves));
-    T.directMax = 63;                                           // emitted in walk order
-    HIPCHK(c, tlas_finish(T, d.stream));
-    HIPCHK(c, tlas_inflate(T, d.stream));
-    int flags[4] = {1, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, T.flags, sizeof(flags), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    if (flags[0] != 0 || flags[1] != 0 || leaves <= 0 || (int64_t)T.nT + T.nTI >= kEnd) return HRT_OK;      // an instance that is not a fast sphere after all
-    // leaf slot of the uploaded tree -> leaf slot of this one (both list every instance once)
-    if (T.nTI != (int)nSlots) return HRT_OK;
-    std::vector<int32_t> mine((size_t)nSlots), slotOfInst((size_t)c->n_inst, -1), map((size_t)nSlots);
-    HIPCHK(c, hipMemcpyAsync(mine.data(), T.tlasInst, (size_t)nSlots * 4, hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    for (int64_t a = 0; a < nSlots; a++)
-    {
-        if (mine[(size_t)a] < 0 || mine[(size_t)a] >= c->n_inst || slotOfInst[(size_t)mine[(size_t)a]] >= 0) return HRT_OK;
-        slotOfInst[(size_t)mine[(size_t)a]] = (int32_t)a;
-    }
-    for (int64_t o = 0; o < nSlots; o++) map[(size_t)o] = slotOfInst[(size_t)uploadedSlots[o]];
-    if (d.tl2mem[14]) { (void)hipFree(d.tl2mem[14]); d.tl2mem[14] = nullptr; }
-    HIPCHK(c, hipMalloc(&d.tl2mem[14], (size_t)nSlots * 4));
-    HIPCHK(c, hipMemcpy(d.tl2mem[14], map.data(), (size_t)nSlots * 4, hipMemcpyHostToDevice));
-    d.tl2 = T;
-    d.dpackedAny = d.dpacked;
-    d.dpackedAny.tlas = T.tlas; d.dpackedAny.finst = T.finst; d.dpackedAny.nTlas = T.nT;
-    d.dpackedAny.tlasX = T.tlasX; d.dpackedAny.nTlasX = T.nT + T.nTI;
-    d.dpackedAny.slotMap = (const int*)d.tl2mem[14];
-    d.dpackedAny.tlasXO = nullptr; d.dpackedAny.xStride = 0; d.dpackedAny.xAxes = 0; d.dpackedAny.tlasO = nullptr; d.dpackedAny.oStride = 0;
-    d.ordX = d.ordP = 0;
-    if (d.tl2mem[17]) { (void)hipFree(d.tl2mem[17]); d.tl2mem[17] = nullptr; }
-    HIPCHK(c, hipMalloc(&d.tl2mem[17], (size_t)nSlots * 4));
-    if (d.tl2mem[15]) { (void)hipFree(d.tl2mem[15]); d.tl2mem[15] = nullptr; }
-    // Which signs select a numbering: the two axes along which the instances are spread most (extent of the box centres between their
-    // 5th and 95th percentile: one huge ground sphere must not count) -- measured on config 3 (22 k records, 0.7 MB a copy), every walk
-    // ordered: x and z 16.2 ms, z 16.8, x 16.7, all three 18.1, none 17.5, y alone 18.9 (along y the builder's order, ground first, is the
-    // better one: one sphere test bounds every ray that goes down).  The copies need not fit the L2: with only the closest-hit walks
-    // on them, frames of 30 001 / 100 001 instances at 4 spp go 10.65 -> 9.4 / 14.9 -> 10.7 ms with four copies of 2.1 / 7.4 MB; the
-    // budget only bounds the memory a huge scene may take.
-    const int nX = T.nT + T.nTI;
-#ifndef HRT_ORDERED_BUDGET_MB       // A/B
-#define HRT_ORDERED_BUDGET_MB 1024
-#endif
-    constexpr size_t kOrderedBudget = (size_t)HRT_ORDERED_BUDGET_MB << 20;
-    int axes = 0;
-    {
-        float ext[3];
-        std::vector<float> v(inst.size());
-        for (int a = 0; a < 3; a++)
-        {
-            for (size_t i = 0; i < inst.size(); i++)
-                v[i] = a == 0 ? inst[i].worldBoundsMin.X + inst[i].worldBoundsMax.X : (a == 1 ? inst[i].worldBoundsMin.Y + inst[i].worldBoundsMax.Y : inst[i].worldBoundsMin.Z + inst[i].worldBoundsMax.Z);
-            for (float& x : v) if (!std::isfinite(x)) x = 0.f;       // (an ordering for std::sort; infinite boxes are legal here)
-            std::sort(v.begin(), v.end());
-            ext[a] = v[v.size() - 1 - v.size() / 20] - v[v.size() / 20];
-        }
-        int order[3] = {0, 1, 2};
-        std::sort(order, order + 3, [&](int p, int q) { return ext[p] > ext[q] || (ext[p] == ext[q] && p < q); });
-        for (int k = 0; k < 2; k++)
-            if (ext[order[k]] > 0.f && ext[order[k]] >= 0.25f * ext[order[0]] && (size_t)nX * sizeof(NodeQ) * (size_t)ord_copies(axes | (1 << order[k])) <= kOrderedBudget)
-                axes |= 1 << order[k];
-    }
-    const int copies = ord_copies(axes);
-    if (axes != 0 && (int64_t)nX * copies < kEnd)
-    {
-        std::vector<NodeQ> X((size_t)nX), all((size_t)nX * (size_t)copies);
-        std::vector<int> from((size_t)(nX + T.nT) * (size_t)copies);
-        HIPCHK(c, hipMemcpy(X.data(), T.tlasX, (size_t)nX * sizeof(NodeQ), hipMemcpyDeviceToHost));
-        bool ok = true;
-        for (int o = 0; ok && o < copies; o++)
-        {
-            int sign[3] = {0, 0, 0};
-            for (int a = 0; a < 3; a++)      // the copy bit of axis a = the index of a direction that is positive along a only
-                if (axes & (1 << a)) sign[a] = (ord_copy(axes, a == 0 ? 1.f : -1.f, a == 1 ? 1.f : -1.f, a == 2 ? 1.f : -1.f) & o) ? 1 : -1;
-            ok = reorder_second_tree(X, sign, o * nX, all.data() + (size_t)o * (size_t)nX, from.data() + (size_t)o * (size_t)nX, true);
-        }
-        // ... and of the plain node array, for launch 1 (both in one allocation: the inlined copies first)
-        const int nP = T.nT;
-        std::vector<NodeQ> Pn((size_t)nP), allP((size_t)nP * (size_t)copies);
-        HIPCHK(c, hipMemcpy(Pn.data(), T.tlas, (size_t)nP * sizeof(NodeQ), hipMemcpyDeviceToHost));
-        for (int o = 0; ok && o < copies; o++)
-        {
-            int sign[3] = {0, 0, 0};
-            for (int a = 0; a < 3; a++)
-                if (axes & (1 << a)) sign[a] = (ord_copy(axes, a == 0 ? 1.f : -1.f, a == 1 ? 1.f : -1.f, a == 2 ? 1.f : -1.f) & o) ? 1 : -1;
-            ok = reorder_second_tree(Pn, sign, o * nP, allP.data() + (size_t)o * (size_t)nP, from.data() + all.size() + (size_t)o * (size_t)nP, false);
-        }
-        if (ok)
-        {
-            HIPCHK(c, hipMalloc(&d.tl2mem[15], (all.size() + allP.size()) * sizeof(NodeQ)));
-            HIPCHK(c, hipMemcpy(d.tl2mem[15], all.data(), all.size() * sizeof(NodeQ), hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy((NodeQ*)d.tl2mem[15] + all.size(), allP.data(), allP.size() * sizeof(NodeQ), hipMemcpyHostToDevice));
-            d.dpackedAny.tlasXO = (const NodeQ*)d.tl2mem[15]; d.dpackedAny.xStride = nX; d.dpackedAny.xAxes = axes;
-            d.dpackedAny.tlasO = (const NodeQ*)d.tl2mem[15] + all.size(); d.dpackedAny.oStride = nP;
-            if (d.tl2mem[16]) { (void)hipFree(d.tl2mem[16]); d.tl2mem[16] = nullptr; }
-            HIPCHK(c, hipMalloc(&d.tl2mem[16], from.size() * sizeof(int)));
-            HIPCHK(c, hipMemcpy(d.tl2mem[16], from.data(), from.size() * sizeof(int), hipMemcpyHostToDevice));
-            d.ordX = all.size(); d.ordP = allP.size();
-        }
-    }
-    d.any_ok = true; d.any_built = true;
-    return HRT_OK;
-}
-
-// After a scene update: the second tree keeps its topology and takes the new boxes (instance records and spheres are shared with the
-// tree in use and already updated), as long as the scene is still what the second tree is exact for -- every instance a fast sphere
-// with a regular box (the flags of its own finish pass), the tree in use a device refit / rebuild (unions of regular boxes: nested,
-// every instance once).  A new topology of the tree in use needs a new slot map.  Otherwise the walks go back to the tree in use.
-int refit_second_tree(hrt_ctx* c, DeviceState& d, bool newTopologyInUse, bool sceneStillFits)
-{
-    d.any_ok = false;
-    if (!d.any_built || !sceneStillFits || !c->own_in_world) return HRT_OK;
-    const TlasDevice& T2 = d.tl2;
-    if (d.tl.nTI != T2.nTI) return HRT_OK;
-    HIPCHK(c, tlas_finish(T2, d.stream));
-    HIPCHK(c, tlas_inflate(T2, d.stream));
-    int flags[4] = {1, 1, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, T2.flags, sizeof(flags), hipMemcpyDeviceToHost, d.stream));
-    if (newTopologyInUse) HIPCHK(c, tlas_slot_map(d.tl.tlasInst, T2.tlasInst, (int*)d.tl2mem[17], (int*)d.tl2mem[14], T2.nTI, d.stream));
-    if (d.dpackedAny.tlasXO)
-    {
-        HIPCHK(c, tlas_refresh_copies((NodeQ*)d.tl2mem[15], T2.tlasX, (const int*)d.tl2mem[16], (int)d.ordX, d.stream));
-        HIPCHK(c, tlas_refresh_copies((NodeQ*)d.tl2mem[15] + d.ordX, T2.tlas, (const int*)d.tl2mem[16] + d.ordX, (int)d.ordP, d.stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    d.any_ok = flags[0] == 0 && flags[1] == 0;
-    return HRT_OK;
-}
-
-} // namespace
-
-namespace {
-
-// Shared tail of the scene updates: `mutate` enqueues what changes the instance records on one device (staging buffers it
-// allocates go into the vector and are freed here), then the TLAS is refitted / rebuilt per `policy` and the walkers' view of
-// the tree is refreshed.
-int apply_update(hrt_ctx* c, int policy, const char* who, const std::function<int(DeviceState&, std::vector<void*>&)>& mutate, hrt_bvh_update_stats* st)
-{
-    if (policy != HRT_REBUILD_AUTO && policy != HRT_REBUILD_FORCE_REFIT && policy != HRT_REBUILD_FORCE_REBUILD)
-        return fail(c, HRT_ERR_INVALID_ARG, std::string(who) + ": unknown policy");
-    if (!c->packed_ok) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": the scene exceeds the limits of the packed layout");
-    if (c->n_inst <= 0) return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": the scene has no instances");
-    if (policy != HRT_REBUILD_FORCE_REBUILD && !c->refit_ok && !c->tlas_on_device)
-    {
-        if (policy == HRT_REBUILD_FORCE_REFIT)
-            return fail(c, HRT_ERR_INVALID_STATE, std::string(who) + ": this TLAS cannot be refitted (a node has several parents or more than 64 children); use HRT_REBUILD_FORCE_REBUILD");
-        policy = HRT_REBUILD_FORCE_REBUILD;
-    }
-    int rc = hrt_synchronize(c, nullptr);
-    if (rc != HRT_OK) return rc;
-    hrt_bvh_update_stats out; std::memset(&out, 0, sizeof(out));
-    bool first = true;
-    for (DeviceState& d : c->dev)
-    {
-        HIPCHK(c, hipSetDevice(d.device_id));
-        TlasDevice& T = d.tl;
-        hipEvent_t e0 = d.ev[0][0], e1 = d.ev[0][1];
-        HIPCHK(c, hipEventRecord(e0, d.stream));
-        int h_flags[4]; float h_cost[2] = {1.f, 0.f};
-        auto finish_and_read = [&]() -> int {
-            HIPCHK(c, tlas_finish(T, d.stream));
-            HIPCHK(c, hipMemcpyAsync(h_flags, T.flags, sizeof(h_flags), hipMemcpyDeviceToHost, d.stream));
-            HIPCHK(c, hipMemcpyAsync(h_cost, T.cost, sizeof(h_cost), hipMemcpyDeviceToHost, d.stream));
-            HIPCHK(c, hipStreamSynchronize(d.stream));
-            return HRT_OK;
-        };
-        auto keep_as_base = [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(T.saBase, T.sa, (size_t)T.nT * 4, hipMemcpyDeviceToDevice, d.stream));
-            d.tlas_base_valid = true;
-            return HRT_OK;
-        };
-        if (!d.tlas_base_valid && policy != HRT_REBUILD_FORCE_REBUILD)
-        {   // node areas of the tree as it was built: taken once, before anything moves
-            HIPCHK(c, tlas_finish(T, d.stream));
-            if ((rc = keep_as_base()) != HRT_OK) return rc;
-        }
-        d.any_ok = false;                      // the second tree describes the scene as it was: refit_second_tree brings it back below
-        std::vector<void*> staged;
-        struct StagedGuard {               // staging buffers of `mutate` are freed on every way out (their copies are ordered on d.stream)
-            std::vector<void*>& v; hipStream_t st;
-            ~StagedGuard() { if (!v.empty()) { (void)hipStreamSynchronize(st); for (void* p : v) (void)hipFree(p); } }
-        } stagedGuard{staged, d.stream};
-        if ((rc = mutate(d, staged)) != HRT_OK) return rc;
-        int action = policy == HRT_REBUILD_FORCE_REBUILD ? HRT_REBUILD_FORCE_REBUILD : HRT_REBUILD_FORCE_REFIT;
-        if (policy == HRT_REBUILD_AUTO && !d.tlas_lbvh) action = HRT_REBUILD_FORCE_REBUILD;   // an uploaded tree: the device-built one costs as much as a refit and walks faster
-        float growthRefit = 0.f;
-        int rebuiltLeaves = 0;
-        if (action == HRT_REBUILD_FORCE_REFIT)
-        {
-            if ((rc = finish_and_read()) != HRT_OK) return rc;
-            growthRefit = h_cost[0];
-            if (policy == HRT_REBUILD_AUTO && growthRefit > kAutoRebuildGrowth) action = HRT_REBUILD_FORCE_REBUILD;
-        }
-        if (action == HRT_REBUILD_FORCE_REBUILD)
-        {
-            if ((rc = ensure_lbvh_scratch(c, d)) != HRT_OK) return rc;
-            HIPCHK(c, tlas_rebuild_topology(T, d.stream, &rebuiltLeaves));
-            T.directMax = 63;                                           // emitted in walk order
-            if ((rc = finish_and_read()) != HRT_OK) return rc;
-            if ((rc = keep_as_base()) != HRT_OK) return rc;
-            h_cost[0] = 1.f;                                            // as built
-            d.tlas_lbvh = true;
-        }
-        HIPCHK(c, hipEventRecord(e1, d.stream));
-        HIPCHK(c, hipEventSynchronize(e1));
-        for (void* p : staged) (void)hipFree(p);
-        staged.clear();
-        // the walkers' view of the tree
-        const bool general = h_flags[0] != 0;
-        d.dpacked.nTlas = T.nT;
-        const bool inl = !general && !c->feat_alpha && (int64_t)T.nT + T.nTI < kEnd;
-        d.dpacked.tlasX = inl ? (const NodeQ*)d.packed[6] : nullptr;
-        d.dpacked.nTlasX = inl ? T.nT + T.nTI : 0;
-        // the second tree follows the scene (same topology, new boxes) or stands down
-        if ((rc = refit_second_tree(c, d, action == HRT_REBUILD_FORCE_REBUILD, !general && !c->feat_alpha && h_flags[1] == 0)) != HRT_OK) return rc;
-        if (first)
-        {
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-            out.action = action; out.tlas_nodes = T.nT; out.tlas_slots = T.nTI; out.general_instances = general ? 1 : 0;
-            out.growth_refit = growthRefit; out.growth_final = h_cost[0]; out.sah_cost = h_cost[1]; out.device_ms = ms;
-            if (action == HRT_REBUILD_FORCE_REBUILD) { c->tlas_leaves = rebuiltLeaves; c->refit_ok = true; }
-            c->packed_feat = c->feat_alpha ? 3 : (general ? 1 : 0);
-            // the leaf sweep skips box tests the reference makes, which is only sound over nested boxes: the device's trees are unions of
-            // the instances' worldBounds, so it takes every fast-sphere instance's own box to lie inside its worldBounds
-            // ... and every worldBounds to be a regular box (no NaN bound, min <= max: h_flags[1]), or the unions are not nested
-            c->flat_leaves = (!general && !c->feat_alpha && c->own_in_world && h_flags[1] == 0 && c->tlas_leaves > 0 && c->tlas_leaves <= kFlatMaxLeaves) ? c->tlas_leaves : 0;
-            c->n_tlas = T.nT; c->n_slots = T.nTI;
-            c->small_scene = (c->n_tlas + c->n_blas) <= kSmallSceneNodes;
-            c->tlas_on_device = true;
-            first = false;
-        }
-    }
-    if (st) *st = out;
-    return HRT_OK;
-}
-
-} // namespace
-
-int hrt_scene_update_instances(hrt_ctx* c, const int32_t* ids, int32_t n, const hrt_affine3x4* xf, int32_t policy, hrt_bvh_update_stats* st)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_instances: no scene uploaded");
-    if (n < 0 || (n > 0 && (!ids || !xf))) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_instances: n instances need ids and transforms");
-    {
-        std::vector<uint8_t> seen((size_t)std::max<int64_t>(c->n_inst, 0), 0);
-        for (int i = 0; i < n; i++)
-        {
-            if (ids[i] < 0 || ids[i] >= c->n_inst) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_instances: instance id out of range");
-            if (seen[(size_t)ids[i]]++) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_instances: instance id listed twice");
-        }
-    }
-    return apply_update(c, policy, "hrt_scene_update_instances", [&](DeviceState& d, std::vector<void*>& staged) -> int {
-        if (n <= 0) return HRT_OK;
-        const size_t idb = ((size_t)n * 4 + 63) & ~(size_t)63;
-        void* buf = nullptr;
-        HIPCHK(c, hipMalloc(&buf, idb + (size_t)n * sizeof(hrt_affine3x4)));
-        staged.push_back(buf);
-        HIPCHK(c, hipMemcpyAsync(buf, ids, (size_t)n * 4, hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, hipMemcpyAsync((char*)buf + idb, xf, (size_t)n * sizeof(hrt_affine3x4), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(c, tlas_set_transforms(d.tl, (const int32_t*)buf, (const hrt_affine3x4*)((char*)buf + idb), n, d.stream));
-        return HRT_OK;
-    }, st);
-}
-catch (...) { return on_exception(c, "hrt_scene_update_instances"); }
-
-int hrt_scene_update_positions(hrt_ctx* c, int64_t first, int64_t n, const hrt_float3* positions, int32_t policy, hrt_bvh_update_stats* st)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_positions: no scene uploaded");
-    if (first < 0 || n < 0 || first + n > c->n_positions || (n > 0 && !positions))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_positions: vertex range outside meshPositions");
-    if (!c->blas_refit_ok)
-        return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_positions: a triangle-mesh BLAS of this scene cannot be refitted (shared or overlapping node ranges, unreachable nodes)");
-    const bool rebuildBlas = policy >= 0 && (policy & HRT_REBUILD_BLAS) != 0;
-    if (policy >= 0) policy &= ~HRT_REBUILD_BLAS;
-    if (rebuildBlas && !c->blas_rebuild_ok)
-        return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_positions: a triangle-mesh BLAS of this scene cannot be rebuilt on the device (its leaves do not list their triangles in one region of triPrimIdx)");
-    int blasAction = 0; float blasGrowth = 0.f;
-    const int rc = apply_update(c, policy, "hrt_scene_update_positions", [&](DeviceState& d, std::vector<void*>&) -> int {
-        const bool meshes = d.n_mesh_inst > 0;
-        d.tl_ok = false;                                // the reduced trees hold copies of the boxes as uploaded: walks go back to the plain walker
-        auto keep_base = [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(d.bl.saBase, d.bl.sa, (size_t)d.bl.nB * 4, hipMemcpyDeviceToDevice, d.stream));
-            d.blas_base_valid = true;
-            return HRT_OK;
-        };
-        auto rebuild_all = [&]() -> int {
-            int rc2 = ensure_lbvh_scratch(c, d);
-            if (rc2 != HRT_OK) return rc2;
-            for (const MeshJob& J : c->mesh_jobs) HIPCHK(c, blas_rebuild_mesh(d.tl, d.bl, J, d.stream, nullptr));
-            return HRT_OK;
-        };
-        int rc2;
-        if (meshes && !d.blas_base_valid && !rebuildBlas)
-        {   // node areas of the BLASes as they were built: taken once, before the first vertex moves
-            HIPCHK(c, blas_refit(d.bl, 1, d.stream));
-            if ((rc2 = keep_base()) != HRT_OK) return rc2;
-        }
-        if (n > 0) HIPCHK(c, hipMemcpyAsync((hrt_float3*)d.scene[7] + first, positions, (size_t)n * sizeof(hrt_float3), hipMemcpyHostToDevice, d.stream));
-        bool rebuilt = false;
-        if (rebuildBlas && !c->mesh_jobs.empty()) { if ((rc2 = rebuild_all()) != HRT_OK) return rc2; rebuilt = true; }
-        if (meshes) HIPCHK(c, blas_refit(d.bl, 1, d.stream));
-        float growth = 0.f;
-        if (meshes && !rebuilt)
-        {
-            HIPCHK(c, blas_growth(d.bl, 1, d.stream));
-            HIPCHK(c, hipMemcpyAsync(&growth, d.bl.grow, 4, hipMemcpyDeviceToHost, d.stream));
-            HIPCHK(c, hipStreamSynchronize(d.stream));
-            if (policy == HRT_REBUILD_AUTO && growth > kAutoRebuildGrowth && c->blas_rebuild_ok && !c->mesh_jobs.empty())
-            {
-                if ((rc2 = rebuild_all()) != HRT_OK) return rc2;
-                HIPCHK(c, blas_refit(d.bl, 1, d.stream));
-                rebuilt = true;
-            }
-        }
-        if (rebuilt && (rc2 = keep_base()) != HRT_OK) return rc2;
-        if (&d == &c->dev[0]) { blasAction = meshes ? (rebuilt ? HRT_REBUILD_FORCE_REBUILD : HRT_REBUILD_FORCE_REFIT) : 0; blasGrowth = growth; }
-        HIPCHK(c, tlas_rebound_instances(d.tl, (const int32_t*)d.blaux[5], d.n_mesh_inst, d.stream));
-        return HRT_OK;
-    }, st);
-    if (rc == HRT_OK && st) { st->blas_action = blasAction; st->blas_growth = blasGrowth; }
-    return rc;
-}
-catch (...) { return on_exception(c, "hrt_scene_update_positions"); }
-
-int hrt_scene_update_spheres(hrt_ctx* c, int64_t first, int64_t n, const hrt_sphere* spheres, int32_t policy, hrt_bvh_update_stats* st)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    c->prog.valid = false;                     // a progressive frame cannot be continued across this call
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_spheres: no scene uploaded");
-    if (first < 0 || n < 0 || first + n > c->n_spheres || (n > 0 && !spheres))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_update_spheres: range outside spheres");
-    if (!c->blas_refit_ok)
-        return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_update_spheres: a BLAS of this scene cannot be refitted (shared or overlapping node ranges, unreachable nodes)");
-    return apply_update(c, policy, "hrt_scene_update_spheres", [&](DeviceState& d, std::vector<void*>&) -> int {
-        if (n > 0) HIPCHK(c, hipMemcpyAsync((hrt_sphere*)d.scene[5] + first, spheres, (size_t)n * sizeof(hrt_sphere), hipMemcpyHostToDevice, d.stream));
-        if (d.n_sphere_inst > 0) HIPCHK(c, blas_refit(d.bl, 2, d.stream));
-        HIPCHK(c, tlas_rebound_instances(d.tl, (const int32_t*)d.blaux[7], d.n_sphere_inst, d.stream));
-        return HRT_OK;
-    }, st);
-}
-catch (...) { return on_exception(c, "hrt_scene_update_spheres"); }
-
-int hrt_scene_download_array(hrt_ctx* c, int dev, int array, void* dst, int64_t cap, int64_t* count)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_download_array: no scene uploaded");
-    if (dev < 0 || dev >= (int)c->dev.size() || array < 0 || array >= 15) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_download_array: device slot or array index out of range");
-    int rc = hrt_synchronize(c, nullptr);
-    if (rc != HRT_OK) return rc;
-    const int64_t have = array == 0 ? c->n_tlas : (array == 1 ? c->n_slots : c->scene_count[array]);
-    if (count) *count = have;
-    if (!dst) return HRT_OK;
-    if (cap < have) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_download_array: destination too small");
-    DeviceState& d = c->dev[(size_t)dev];
-    HIPCHK(c, hipSetDevice(d.device_id));
-    if (have > 0) HIPCHK(c, hipMemcpyAsync(dst, d.scene[array], (size_t)have * kSceneElem[array], hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    return HRT_OK;
-}
-catch (...) { return on_exception(c, "hrt_scene_download_array"); }
-
-int hrt_scene_download_tlas(hrt_ctx* c, int dev, hrt_bvh_node* nodes, int64_t capN, int32_t* idx, int64_t capI, hrt_instance* inst, int64_t capInst, int64_t* counts)
-try {
-    if (!c) return HRT_ERR_INVALID_ARG;
-    if (!c->scene_ready) return fail(c, HRT_ERR_INVALID_STATE, "hrt_scene_download_tlas: no scene uploaded");
-    if (dev < 0 || dev >= (int)c->dev.size()) return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_download_tlas: device slot out of range");
-    int rc = hrt_synchronize(c, nullptr);
-    if (rc != HRT_OK) return rc;
-    DeviceState& d = c->dev[(size_t)dev];
-    const int64_t have[3] = {c->n_tlas, c->n_slots, c->n_inst};
-    if (counts) { counts[0] = have[0]; counts[1] = have[1]; counts[2] = have[2]; }
-    if ((nodes && capN < have[0]) || (idx && capI < have[1]) || (inst && capInst < have[2]))
-        return fail(c, HRT_ERR_INVALID_ARG, "hrt_scene_download_tlas: destination too small");
-    HIPCHK(c, hipSetDevice(d.device_id));
-    if (nodes && have[0] > 0) HIPCHK(c, hipMemcpyAsync(nodes, d.scene[0], (size_t)have[0] * sizeof(hrt_bvh_node), hipMemcpyDeviceToHost, d.stream));
-    if (idx && have[1] > 0) HIPCHK(c, hipMemcpyAsync(idx, d.scene[1], (size_t)have[1] * 4, hipMemcpyDeviceToHost, d.stream));
-    if (inst && have[2] > 0) HIPCHK(c, hipMemcpyAsync(inst, d.scene[2], (size_t)have[2] * sizeof(hrt_instance), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(c, hipStreamSynchronize(d.stream));
-    return HRT_OK;
-}
-catch (...) { return on_exception(c, "hrt_scene_download_tlas"); }
 
 int hrt_reset_history(hrt_ctx* c)
 try {
@@ -3811,9 +2378,10 @@ catch (...) { return on_exception(c, "hrt_math_exhaustive"); }
 // test hooks of the treelet cut (include/hrt_test_hooks.h)
 extern "C" int hrt_debug_set_treelet_limits(int bytes, int min_nodes, int min_blas_nodes)
 {
-    g_treelet_limits = TreeletLimits{};
-    if (bytes > 0) { g_treelet_limits.bytes = bytes; g_treelet_limits.minNodes = min_nodes; g_treelet_limits.minBlasNodes = min_blas_nodes; }
-    if (min_blas_nodes < 0) g_treelet_limits.minBlasNodes = 0x7FFFFFFF;
+    TreeletLimits& lim = treelet_limits();
+    lim = TreeletLimits{};
+    if (bytes > 0) { lim.bytes = bytes; lim.minNodes = min_nodes; lim.minBlasNodes = min_blas_nodes; }
+    if (min_blas_nodes < 0) lim.minBlasNodes = 0x7FFFFFFF;
     return 0;
 }
 
@@ -3842,6 +2410,19 @@ try {
     return HRT_OK;
 }
 catch (...) { return on_exception(nullptr, "hrt_debug_treelets"); }
+
+// host-only test hook of the scene validator (include/hrt_test_hooks.h): the text hrt_scene_upload would fail with
+extern "C" int hrt_debug_validate_scene(const hrt_scene_desc* s, char* msg, int cap)
+try {
+    if (!s) return HRT_ERR_INVALID_ARG;
+    if (msg && cap > 0) msg[0] = 0;
+    PackedHost ph;
+    const std::string verr = validate_and_pack(s, ph);
+    if (verr.empty()) return HRT_OK;
+    if (msg && cap > 0) { std::strncpy(msg, verr.c_str(), (size_t)cap - 1); msg[cap - 1] = 0; }
+    return HRT_ERR_INVALID_ARG;
+}
+catch (...) { return on_exception(nullptr, "hrt_debug_validate_scene"); }
 #endif // HRT_TEST_HOOKS
 
 #ifdef HRT_TL_STATS
@@ -3867,7 +2448,7 @@ extern "C" int hrt_debug_pt_stats(unsigned long long* out64)
 #endif
 
 #ifdef HRT_TEST_HOOKS
-// ---- host-only test hooks of the second tree (include/hip_raytrace.h)
+// ---- host-only test hooks of the second tree (include/hrt_test_hooks.h; the code is hrt_scene_pack.hip's)
 extern "C" {
 
 int hrt_debug_second_tree_topology(const hrt_instance* instances, int32_t n, int32_t* order, int32_t* link, int32_t* skip, int32_t* count,

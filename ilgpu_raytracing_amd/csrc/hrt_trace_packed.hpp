@@ -30,7 +30,7 @@ namespace hrt {
 constexpr int kEnd = 0x0FFFFFFF;            // packed form of the -1 link
 
 struct NodeQ { float4 lo, hi; };            // lo.w = bits(left | first), hi.w = bits(skip | count << 28)
-struct FInst { float4 a, b, c; };           // a.w = bits(flags), b.w = bits(index); see hrt_runtime.hip pack_scene()
+struct FInst { float4 a, b, c; };           // a.w = bits(flags), b.w = bits(index); see validate_and_pack (hrt_scene_pack.hip)
 struct FTri  { float4 v0, v1, v2; };        // v0.w = bits(triIndex), v1.w = bits(matIndex), v2.w = bits(flags)
 
 enum { FI_FAST_SPHERE = 1, FI_IDENTITY = 2, FI_SPHERESET = 4 };

@@ -41,6 +41,9 @@ struct DTreelets {
     int nTl, nRed, redLds, tlBytesMax;
 };
 
+// dynamic LDS a walk kernel asks for (laid out by tl_shared, hrt_walker_tl.hpp); the upload checks it against the device's limit
+inline size_t tl_shared_bytes(int tlRegion, int redLds, int histBins) { return (size_t)tlRegion + (size_t)redLds * 32 + 9 * 256 * 4 + (size_t)histBins * 4 + 64; }
+
 struct TreeletsHost {
     std::vector<NodeQ> red;
     std::vector<Treelet> tl;

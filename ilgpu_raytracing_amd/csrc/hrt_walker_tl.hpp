@@ -53,7 +53,7 @@ struct TlQueues {                // per batch lane and walk kind
     int* curs;                   // [nTl] scatter cursors
 };
 
-// dynamic LDS of the walk kernels: [treelet][reduced-tree prefix][ray park][histogram][misc]
+// dynamic LDS of the walk kernels: [treelet][reduced-tree prefix][ray park][histogram][misc]; its size: tl_shared_bytes (hrt_treelets.hpp)
 struct TlShared { float4* tl; const float4* red; float (*park)[256]; int* hist; int* misc; };
 HRT_D TlShared tl_shared(int tlRegion, int redLds, int histBins)
 {
@@ -67,7 +67,6 @@ HRT_D TlShared tl_shared(int tlRegion, int redLds, int histBins)
     s.misc = reinterpret_cast<int*>(p);
     return s;
 }
-inline size_t tl_shared_bytes(int tlRegion, int redLds, int histBins) { return (size_t)tlRegion + (size_t)redLds * 32 + 9 * 256 * 4 + (size_t)histBins * 4 + 64; }
 
 // fetch(i, ray): world ray of entry i (false: the entry carries none); done(i, result) as in walk_queue.
 // PHASE 0 / 2: nextSeg hands out runs of ENTRIES (path slots / shadow requests); PHASE 1: runs of POSITIONS in Q.sorted.

@@ -23,7 +23,7 @@ int  hrt_math_probe(hrt_ctx* ctx, int fn, int n, const float* x, const float* y,
 int  hrt_math_exhaustive(hrt_ctx* ctx, int which, uint64_t* mismatches, uint32_t* first_bad);
 
 /* test hooks, host code only (no device, no context): what hrt_scene_upload computes on the host for the SECOND tree of a scene of
- * many one-sphere instances.
+ * many one-sphere instances (csrc/hrt_scene_pack.hip).
  * hrt_debug_second_tree_topology: the binned-SAH topology over the world bounds of n instances, in walk order.  order[n]: instance
  *   of every leaf slot; per node i < *n_nodes (arrays of capacity 2 n): link[i] = first slot of a leaf / index of the first child,
  *   skip[i] = next node when node i is missed (0x0FFFFFFF: none), count[i] = instances of a leaf (0: inner node), parent[i].
@@ -49,6 +49,12 @@ int  hrt_debug_set_treelet_limits(int bytes, int min_nodes, int min_blas_nodes);
 int  hrt_debug_treelet_count(hrt_ctx* ctx);
 int  hrt_debug_treelets(const hrt_scene_desc* scene, int bytes, int min_nodes, int min_blas_nodes,
                         float* blas, float* red, int32_t* red_orig, int32_t* treelets, int32_t* red_of_root, int64_t* counts);
+
+/* test hook, host code only (no device, no context): the scene validator of hrt_scene_upload (csrc/hrt_scene_pack.hip,
+ * validate_and_pack) on a scene whose counts are >= 0 and whose non-empty arrays have pointers (what the upload checks before it).
+ * Returns HRT_OK, or HRT_ERR_INVALID_ARG with the validator's text -- what hrt_scene_upload reports behind "hrt_scene_upload: " --
+ * copied into msg (cap bytes, always terminated; msg may be NULL). */
+int  hrt_debug_validate_scene(const hrt_scene_desc* scene, char* msg, int cap);
 
 #ifdef __cplusplus
 }

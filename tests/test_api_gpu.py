@@ -200,3 +200,39 @@ def test_second_tree_is_not_built_over_stale_world_bounds(orc, renderer):
             H.assert_outputs_equal(ref, got)
     finally:
         s2 = engine.Scene(); scenes.build_config2(s2); renderer.commit(s2)
+
+
+@pytest.fixture(scope="module")
+def committed_small_scene(renderer):
+    """The valid scene of tests/scene_mutations.py committed to the shared renderer, and a 32x32, 1 spp frame of it."""
+    from tests import scene_mutations as M
+    valid = M.valid_arrays()
+    desc, keep = T.scene_desc_from_arrays(valid)
+    renderer.commit(desc)
+    p = _params(scenes.Config("small", 0, 0, 0, (0.0, 1.0, 4.0), (0.0, 0.8, 0.0)), 32, 32, 1)
+
+    def frame():
+        renderer.reset_history()
+        out, o = T.alloc_outputs(32, 32)
+        renderer.render_params(p, o)
+        return out
+
+    before = frame()
+    assert len(np.unique(before["objectId"])) > 1, "the frame sees none of the scene"
+    yield valid, frame, before
+    s2 = engine.Scene(); scenes.build_config2(s2); renderer.commit(s2)
+
+
+@pytest.mark.parametrize("name", ["tlas_cycle", "tri_prim_idx", "instance_blas_range"])
+def test_upload_rejects_a_malformed_scene_and_keeps_the_committed_one(renderer, committed_small_scene, name):
+    """hrt_scene_upload fails with the validator's own text (csrc/hrt_scene_pack.hip) and validates before it synchronises or frees
+    anything: the scene committed before still renders the same frame, bit for bit.  The malformed scene is rejected on the host and
+    never reaches the device."""
+    import re
+    from tests import scene_mutations as M
+    valid, frame, before = committed_small_scene
+    desc, keep, message = M.mutated_desc(valid, name)
+    with pytest.raises(engine.HrtError, match=re.escape("hrt_scene_upload: " + message)) as e:
+        renderer.commit(desc)
+    assert e.value.code == -1                                        # HRT_ERR_INVALID_ARG
+    H.assert_outputs_equal(before, frame())

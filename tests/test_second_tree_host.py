@@ -1,5 +1,5 @@
-"""Host half of the SECOND tree of scenes of many one-sphere instances (csrc/hrt_runtime.hip: host_sah_topology,
-reorder_second_tree), through the two host-only test hooks of include/hip_raytrace.h -- no GPU.  The pictures cannot depend on
+"""Host half of the SECOND tree of scenes of many one-sphere instances (csrc/hrt_scene_pack.hip: host_sah_topology,
+reorder_second_tree), through the two host-only test hooks of include/hrt_test_hooks.h -- no GPU.  The pictures cannot depend on
 either (the GPU tests compare them with the oracle); what is checked here is that the arrays are the trees the
 walkers assume: a binary tree in walk order over every instance exactly once, and renumberings that are permutations of the same
 records with consistent links and the nearer child first."""

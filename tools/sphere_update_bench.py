@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Moving SPHERES (hrt_scene_update_spheres) in a scene of N one-sphere instances: what a frame costs before the move, after a refit
-and after a device rebuild of the tree in use -- i.e. whether the second tree (hrt_runtime.hip, refit_second_tree) follows the scene.
+and after a device rebuild of the tree in use -- i.e. whether the second tree (hrt_scene.hip, refit_second_tree) follows the scene.
    python tools/sphere_update_bench.py [--counts 10000,100000] [--spp 4]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
