@@ -317,11 +317,16 @@ HRT_D F3 item_centroid(const ItemSrc& S, int i)
 HRT_D unsigned ord_key(float f) { const unsigned u = (unsigned)f2i(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 HRT_D float ord_float(unsigned k) { return i2f((int)((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k)); }
 
+// Per-axis min / max over the centroids that are not NaN.  hrt_fmin / hrt_fmax drop a NaN operand, so a lane without an item
+// carries NaN and a value that is still NaN at the end of the workgroup's reduction stands for "no such centroid here": it
+// must not reach the atomics (as a key a NaN lies beyond every real number, on the side its sign bit chooses).  An axis on
+// which every centroid is NaN keeps the memset keys, which read back as NaN: no extent.
 __global__ void __launch_bounds__(kBlock) k_centroid_bounds(TlasDevice T, ItemSrc S)
 {
     __shared__ float s[6][kBlock / 64];
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    F3 mn = mk3(FLT_MAX, FLT_MAX, FLT_MAX), mx = mk3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
+    const float none = i2f(0x7FC00000);
+    F3 mn = mk3(none, none, none), mx = mn;
     if (i < S.n) { const F3 c = item_centroid(S, i); mn = c; mx = c; }
     float v[6] = {mn.x, mn.y, mn.z, mx.x, mx.y, mx.z};
     for (int d = 32; d > 0; d >>= 1)
@@ -334,7 +339,7 @@ __global__ void __launch_bounds__(kBlock) k_centroid_bounds(TlasDevice T, ItemSr
         const int k = threadIdx.x;
         float r = s[k][0];
         for (int w = 1; w < kBlock / 64; w++) r = k < 3 ? hrt_fmin(r, s[k][w]) : hrt_fmax(r, s[k][w]);
-        if (k < 3) atomicMin(T.cboundsKey + k, ord_key(r)); else atomicMax(T.cboundsKey + k, ord_key(r));
+        if (r == r) { if (k < 3) atomicMin(T.cboundsKey + k, ord_key(r)); else atomicMax(T.cboundsKey + k, ord_key(r)); }
     }
 }
 
@@ -736,7 +741,8 @@ hipError_t blas_rebuild_mesh(const TlasDevice& T, const BlasDevice& B, const Mes
     k_centroid_bounds<<<blocks_for(n), kBlock, 0, s>>>(T, S);
     k_morton<<<blocks_for(n), kBlock, 0, s>>>(T, S);
     size_t bytes = T.sortTmpBytes;
-    e = hipcub::DeviceRadixSort::SortPairs(T.sortTmp, bytes, (const unsigned*)T.keys, T.keysSorted, (const int*)T.vals, (int*)(B.triPrimIdxW + J.leafBase), n, 0, 30, s);
+    // sorted into scratch (T.lstart is free until a limit is chosen): the mesh is not touched before it is known that a tree fits
+    e = hipcub::DeviceRadixSort::SortPairs(T.sortTmp, bytes, (const unsigned*)T.keys, T.keysSorted, (const int*)T.vals, T.lstart, n, 0, 30, s);
     if (e != hipSuccess) return e;
     if (n > 1) k_lbvh_inner<<<blocks_for(n - 1), kBlock, 0, s>>>(T, n, 1);
     // the smallest leaf-size limit whose tree fits the node range of the mesh
@@ -747,8 +753,13 @@ hipError_t blas_rebuild_mesh(const TlasDevice& T, const BlasDevice& B, const Mes
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     int limit = 4;                                   // the reference's BLAS leaf size
     while (limit < 14 && 2 * counts[limit] - 1 > J.nodeCap) limit++;
-    if (2 * counts[limit] - 1 > J.nodeCap) return hipErrorInvalidValue;
+    if (2 * counts[limit] - 1 > J.nodeCap)
+    {   // no limit fits (collapsed leaves are rarely full): nodes, leaf region and triangle records stay as they are
+        if (leafLimitOut) *leafLimitOut = 0;
+        return hipSuccess;
+    }
     if (leafLimitOut) *leafLimitOut = limit;
+    if ((e = hipMemcpyAsync(B.triPrimIdxW + J.leafBase, T.lstart, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(T.lstart, 0, (size_t)(n + 1) * sizeof(int), s)) != hipSuccess) return e;
     k_mark_leaves<<<blocks_for(2 * n - 1), kBlock, 0, s>>>(T, n, limit);
     bytes = T.iscanTmpBytes;

@@ -619,10 +619,17 @@ try {
             d.blas_base_valid = true;
             return HRT_OK;
         };
+        int rebuiltMeshes = 0;
         auto rebuild_all = [&]() -> int {
             int rc2 = ensure_lbvh_scratch(c, d);
             if (rc2 != HRT_OK) return rc2;
-            for (const MeshJob& J : c->mesh_jobs) HIPCHK(c, blas_rebuild_mesh(d.tl, d.bl, J, d.stream, nullptr));
+            rebuiltMeshes = 0;
+            for (const MeshJob& J : c->mesh_jobs)
+            {
+                int limit = 0;
+                HIPCHK(c, blas_rebuild_mesh(d.tl, d.bl, J, d.stream, &limit));
+                if (limit > 0) rebuiltMeshes++;           // 0: no leaf size fits the node range of this mesh; it keeps its topology
+            }
             return HRT_OK;
         };
         int rc2;
@@ -649,7 +656,7 @@ try {
             }
         }
         if (rebuilt && (rc2 = keep_base()) != HRT_OK) return rc2;
-        if (&d == &c->dev[0]) { blasAction = meshes ? (rebuilt ? HRT_REBUILD_FORCE_REBUILD : HRT_REBUILD_FORCE_REFIT) : 0; blasGrowth = growth; }
+        if (&d == &c->dev[0]) { blasAction = meshes ? (rebuilt && rebuiltMeshes > 0 ? HRT_REBUILD_FORCE_REBUILD : HRT_REBUILD_FORCE_REFIT) : 0; blasGrowth = growth; }
         HIPCHK(c, tlas_rebound_instances(d.tl, (const int32_t*)d.blaux[5], d.n_mesh_inst, d.stream));
         return HRT_OK;
     }, st);

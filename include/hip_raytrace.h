@@ -230,6 +230,13 @@ int  hrt_scene_upload(hrt_ctx* ctx, const hrt_scene_desc* scene);
  *     refitted tree have grown, in the geometric mean
  *     over all nodes, to more than 1.5 x the surface area they had when the tree was last built (uploaded or
  *     rebuilt): a measure neither one far-flung instance nor one huge instance dominates.
+ * The rebuilt topology is a function of the instance records alone (tests/lbvh_ref.py restates it): the centroid of an
+ * item is 0.5f * (worldBoundsMin + worldBoundsMax); the centroid bounds are the per-axis min / max over the centroids that are
+ * not NaN, in every layout of the ids (an axis without one has no extent); every axis is cut into 1024 cells with the pitch
+ * of the longest extent, a centroid at or beyond lo + ext lands in cell 1023, one that is NaN or not above lo in cell 0; the
+ * 30-bit Morton keys (x in the highest lane) are sorted stably, equal keys keep id order and are told apart by sorted
+ * position in Karras' construction; a subtree of <= 2 instances whose parent holds more is one leaf; nodes are numbered in
+ * walk order.
  * n may be 0 (re-derive / rebuild only).  Blocking; every device of the context is updated.  The TLAS of a scene
  * updated this way is numbered in walk order; hrt_scene_download_tlas returns it in the reference's layout.
  * A different tree visits the same primitives in another order: results change only where two primitives are
@@ -263,7 +270,14 @@ int  hrt_scene_update_instances(hrt_ctx* ctx, const int32_t* instance_ids, int32
  * geometric mean, to more than 1.5 x their area at the last build.  policy | HRT_REBUILD_BLAS first gives every triangle-mesh BLAS a new topology for the
  * new positions: a Morton-order LBVH over its triangles with leaves of <= 4 like the reference's BLAS, built on the device
  * into the node range and the leaf region of triPrimIdx the mesh already owns (blasNodeCount of its instance shrinks to
- * the new node count).  Another BLAS visits triangles in another order: pixels where two triangles are hit at bit-equal
+ * the new node count).  The construction is the TLAS's (see hrt_scene_update_instances) over the triangle centroids
+ * ((a + b) + c) / 3.f, items always read from the instance's own item list triPrimIdx[primIndexFirst ...], with the smallest
+ * leaf size in 4..14 whose tree (2 leaves - 1 nodes) fits the node range; nodes of the range behind the tree are zeroed, links -1.
+ * Meshes are rebuilt in instance order and each reads its item list as it is at its turn (the reference's builder gives a later
+ * mesh an item window inside an earlier mesh's leaf region, Scene.cs:398-403: its items are what that rebuild left there).
+ * A mesh whose tree does not fit its node range even with leaves of 14 (the range an upload accepts only guarantees room for
+ * FULL leaves) keeps the topology, leaf region and triPrimIdx it has and is refitted; the call succeeds, the other meshes are
+ * rebuilt, and blas_action says rebuild only if at least one mesh got a new topology.  Another BLAS visits triangles in another order: pixels where two triangles are hit at bit-equal
  * distance (shared edges) may change, exactly as they would under a different host builder.
  * Sphere BLASes are untouched.  Blocking; every device of the context is updated. */
 int  hrt_scene_update_positions(hrt_ctx* ctx, int64_t first_vertex, int64_t n, const hrt_float3* positions,
