@@ -99,7 +99,10 @@ enum hrt_render_flags {
     HRT_FLAG_STREAMED     = 1u << 5,  /* force the streamed init/shade/walk/finish/resolve pipeline.  Neither flag:
                                          the library picks by scene size (tiny BVH -> fused).  Identical results.  */
     HRT_FLAG_NO_SYNC      = 1u << 3,  /* enqueue only (outputs must be NULL); collect with hrt_synchronize.
-                                         Up to 128 frames may be in flight; the 129th call drains first.      */
+                                         Up to 128 frames may be in flight; the 129th call drains first.  The
+                                         times and the count of the frames drained there are not reported by
+                                         the next hrt_synchronize (nor by hrt_frame_times): it reports the frames
+                                         enqueued since, kernel_ms and frames alike.                            */
     /* One process per GPU with ReSTIR reuse ON: a tile needs the current G-buffer (worldPos, normalWS, objId) and the
      * previous reservoirs of the WHOLE image (RTRay.cs:339-374, 488-515).  The host then renders a frame in two calls
      * with an all-gather after each (ilgpu_raytracing_amd/tiling.py, RCCL through torch.distributed):
@@ -151,6 +154,16 @@ typedef struct hrt_render_opts {
     int32_t  strip_i;         /* call renders strips s with s % strip_n == strip_i  */
                               /* (load-balanced tiling for one-process-per-GPU hosts) */
 } hrt_render_opts;
+/* Strips are counted from row_begin, not from row 0: strip s holds rows row_begin + 8 s .. row_begin + 8 s + 7, the last one only
+ * the rows below row_end.  A range that begins off a multiple of 8 therefore has strips off the 8-row grid of the image, and its
+ * last strip may be ragged although row_end is not the image's height.
+ * A call may own no strip (strip_i >= S, S = (row_end - row_begin + 7) / 8 the number of strips of the range): it returns HRT_OK,
+ * renders nothing and writes nothing to `outputs`.
+ * A context over nd device slots deals the call's strips again among its slots: slot j renders, and gathers into `outputs`, the
+ * strips s with s % (strip_n * nd) == strip_i + strip_n * j, which is what hrt_device_views of slot j reports as strip_n, strip_i.
+ * A slot may own no strip either.  Row y of [row_begin, row_end) thus belongs to slot j of the call iff
+ * ((y - row_begin) / 8) % (strip_n * nd) == strip_i + strip_n * j.  cameraId (one element, in no row) is delivered by the call
+ * and slot that own strip 0 of a range beginning at row 0. */
 
 /* Device-resident views of the current frame on device slot `dev` (for on-device
  * consumers such as the TAAU/blit kernels or a torch tensor wrapper).  Pointers stay
